@@ -5,9 +5,19 @@ bench.py -- separated audio frames/sec (fwd + SI-SDR/PIT + bwd [+ all-reduce] + 
     python bench.py --gpus 1 --steps 10 --warmup 3
     python bench.py --gpus N ...            (WORLD_SIZE unset: re-executes itself under torch.distributed.run with N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full          (every leg outside the timed region, see below)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR
 
-Rank 0 prints ONE compact JSON line (< 3 KB) as the LAST line of stdout; everything else (per-kernel table, traffic table, the legs'
-descriptions) goes to profiles/bench_detail.json (and gpurun_out/bench_detail.json when that directory exists), named in the line.
+Rank 0 prints ONE compact JSON line (< 3 KB) as the LAST line of stdout.  A plain run does only what the line's headline needs: set up,
+warm up, time the K steps, write the outputs (--dump-outputs), print the line.  --full adds the legs outside the timed region (per-kernel
+roofline pass, fp32-MFMA pass, rocprofv3 traffic passes, inference leg, stock-torch and CPU baselines; each still switched off by its
+--no-* flag) and writes everything else (per-kernel table, traffic table, the legs' descriptions) to profiles/bench_detail.json, named in
+the line.
+
+--dump-outputs DIR: after the timed steps, what the LAST timed step computed, as a caller of the step receives it: DIR/loss.npy (float64),
+DIR/parameters.npy (the parameters after its Adam update), DIR/gradients.npy (its gradient buffer, before the clip scale) and, where the
+step reports one, DIR/pattern.npy (the chosen permutation), float32, at most 64 MB in all (a fixed, seeded sample of an array beyond its
+share).  Model and batch are seeded: the same arguments give the same inputs on every run.
 
 A "step" is one pass of the hot path over one batch resident in HBM.  `roofline` is for ONE kernel instance: the launch class with the
 largest share of the step's kernel time (HIP events around every launch on the launch stream, in a second pass of the same K steps);
@@ -140,7 +150,16 @@ def main():
                          "latent, or trainable / pseudo-inverse (the reference README's other two published rows): linear filterbanks run the fused "
                          "kernel sequence on bases derived from their parameters")
     ap.add_argument("--sink-iters", type=int, default=200, help="sinkpit4: Sinkhorn iterations (the tutorial recipe uses 200; the paper's ablation 10)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs outside the timed region (kernel timing, fp32-MFMA pass, PMC traffic, inference / stock / CPU baselines) "
+                         "and write the detail record; a plain run times the steps and prints the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, parameters, gradients[, pattern]) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_f32_pass = args.no_pmc = args.no_stock = True
     if args.config in ("causal", "dprnn", "dptnet", "galrnet", "sepformer"):
         return legs.bench_dual_path(args)
     if args.batch is None:
@@ -268,6 +287,9 @@ def main():
     elapsed, loss = timed_steps(args.steps)              # THE timed region: K steps, nothing else in it
     my_elapsed = elapsed
     final_loss = float(loss)                             # NOW: a replayed step returns the recorded step's loss buffer, which a later recording (fp32 pass) replaces
+    if args.dump_outputs and rank == 0:                  # before any other leg steps the model again
+        pattern = step.last_pattern if use_seq else None
+        legs.dump_outputs(args.dump_outputs, {"loss": loss.detach().double(), "parameters": step.flat, "gradients": step.gflat, "pattern": pattern})
 
     arith_name = sepkernels.gemm_arith_name()
     by_kernel = roof_g = roof_w = None
@@ -388,7 +410,7 @@ def main():
             detail["hipified_baseline"] = legs.hipified_baseline(mixture, sources)
         if world == 1 and not args.no_cpu_baseline:
             detail["cpu_baseline"] = legs.cpu_baseline()
-        if not dry and (not (args.no_kernel_timing and args.no_pmc and args.no_stock and args.no_cpu_baseline and args.no_f32_pass) or world > 1):
+        if not dry and args.full and (not (args.no_kernel_timing and args.no_pmc and args.no_stock and args.no_cpu_baseline and args.no_f32_pass) or world > 1):
             detail["detail"] = write_detail(detail)    # (the counter passes' child runs and other stripped runs do not overwrite the record)
         print(json.dumps(compact_line(detail)), flush=True)
     if world > 1:

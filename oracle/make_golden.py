@@ -372,6 +372,80 @@ def paper_b16_golden(ConvTasNet, NegSISDR, PIT1d):
     print("paper-best B=16 fp64 reference: loss", loss64.item(), "in {:.0f} s".format(time.time() - t0))
 
 
+# tests/test_oracle_vs_reference_cpu.py: the REFERENCE at paper-best on one utterance off the stride grid (T = 20003: the input-padding
+# branch), fp64, after a perturbation of gamma / beta / alpha: the whole output, PIT loss, permutation and a fingerprint of every parameter
+# gradient (norm, largest magnitude, 64 samples).  The parameters are stored as fingerprints only: default init under the seed + the
+# perturbation below, which the product's class draws the same way (the test checks the fingerprints first).
+PAPER_T20003_SEEDS = {"model": 111, "perturb": 7, "data": 222}
+
+
+def paper_t20003_setup(ConvTasNet):
+    """(fp64 model, mixture, sources) of the fixture, for the reference's class or the product's"""
+    torch.manual_seed(PAPER_T20003_SEEDS["model"])
+    model = ConvTasNet(**PAPER_CFG).double()
+    with torch.no_grad():                                  # default gamma = 1, beta = 0, alpha = 0.25 would hide indexing mistakes
+        g = torch.Generator().manual_seed(PAPER_T20003_SEEDS["perturb"])
+        for name, p in model.named_parameters():
+            if name.endswith("norm.weight") or name.endswith("norm.bias"):
+                p.add_(0.1 * torch.randn(p.shape, generator=g, dtype=torch.float64))
+            elif name.endswith("nonlinear1d.weight") or name.endswith("prelu.weight"):
+                p.add_(0.1 * torch.rand(p.shape, generator=g, dtype=torch.float64))
+    sources = 0.1 * torch.randn(1, 2, 20003, generator=torch.Generator().manual_seed(PAPER_T20003_SEEDS["data"]), dtype=torch.float64)
+    return model, sources.sum(1, keepdim=True), sources
+
+
+def paper_t20003_golden(ConvTasNet, NegSISDR, PIT1d):
+    model, mixture, sources = paper_t20003_setup(ConvTasNet)
+    blob = {"mixture_head": mixture.numpy()[0, 0, :16].copy()}
+    for k, v in model.state_dict().items():
+        blob["pfp/" + k] = np.array([v.sum().item(), v.abs().sum().item()])
+    out = model(mixture)
+    loss, pattern = PIT1d(NegSISDR(), n_sources=2)(out, sources)
+    loss.backward()
+    blob.update({"output": out.detach().numpy(), "loss": np.array(loss.item()), "pattern": pattern.numpy()})
+    for k, p in model.named_parameters():
+        gr = p.grad.reshape(-1)
+        blob["gfp/" + k] = np.concatenate([[gr.norm().item(), gr.abs().max().item()], gr[sample_index(gr.numel())].numpy()])
+    np.savez_compressed(os.path.join(OUT, "convtasnet_paper_t20003.npz"), **blob)
+    print("paper-best T=20003 fp64 reference: loss", loss.item(), "pattern", pattern.tolist())
+
+
+# tests/test_distance_cpu.py::test_against_reference_classes: the reference's criterion classes (src/criterion/distance.py, sdr.py) on the
+# music recipe's (batch, sources, channels, T) layout, fp64: every value and input gradient, per criterion and batch_mean.
+DISTANCE_CASES = [("MeanAbsoluteError", dict(dim=-1, reduction="mean")), ("MeanSquaredError", dict(dim=-1, reduction="mean")),
+                  ("MeanSquaredError", dict(dim=(2, 3), reduction="sum")), ("L1Loss", dict(dim=3)), ("L2Loss", dict(dim=1, reduction="sum")),
+                  ("SDR", dict()), ("NegSDR", dict(reduction="sum"))]
+
+
+def distance_inputs():
+    g = torch.Generator().manual_seed(77)
+    t = torch.randn(3, 4, 2, 333, generator=g, dtype=torch.float64)
+    return t + 0.5 * torch.randn(3, 4, 2, 333, generator=g, dtype=torch.float64), t
+
+
+def distance_golden():
+    import importlib.util
+
+    def load(fname, modname):
+        spec = importlib.util.spec_from_file_location(modname, os.path.join(REF, "criterion", fname))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod
+    rd, rs = load("distance.py", "_ref_distance"), load("sdr.py", "_ref_sdr")
+    x, t = distance_inputs()
+    blob = {}
+    for i, (cls, kw) in enumerate(DISTANCE_CASES):
+        crit = getattr(rd if hasattr(rd, cls) else rs, cls)(**kw)
+        for batch_mean in (True, False):
+            a = x.clone().requires_grad_(True)
+            la = crit(a, t, batch_mean=batch_mean)
+            la.sum().backward()
+            blob.update({"{}/{:d}/value".format(i, batch_mean): la.detach().numpy(), "{}/{:d}/grad".format(i, batch_mean): a.grad.numpy(),
+                         "{}/maximize".format(i): np.array(crit.maximize)})
+    np.savez_compressed(os.path.join(OUT, "distance.npz"), **blob)
+    print("distance: {} cases".format(len(DISTANCE_CASES)))
+
+
 # The reference's TRAINING STEP, several times over (egs/wsj0-mix/common/src/driver.py:141-157: zero_grad, model(mixture), pit_criterion,
 # backward, clip_grad_norm_(max_norm), optimizer.step with torch.optim.Adam -- local/train.py:103-118), on seeded batches, in fp32 as shipped
 # and in fp64: the loss of every step and a fingerprint of the parameters afterwards.  The GPU tier runs the recipe's own step
@@ -520,6 +594,10 @@ if __name__ == "__main__":
         dprnn_full_golden(NegSISDR, PIT1d)
     if not only or "paper_b16" in only:
         paper_b16_golden(ConvTasNet, NegSISDR, PIT1d)
+    if not only or "distance" in only:
+        distance_golden()
+    if not only or "paper_t20003" in only:
+        paper_t20003_golden(ConvTasNet, NegSISDR, PIT1d)
     if not only or "trajectory" in only:
         train_trajectory_golden(ConvTasNet, NegSISDR, PIT1d)
     print("golden vectors written to", OUT)

@@ -1,8 +1,6 @@
 """CPU: criterion/distance.py and criterion/sdr.py:{sdr,SDR,NegSDR} through the CPU emulator of the C ABI, against the
 formulas of reference src/criterion/distance.py:7-285 / src/criterion/sdr.py:6-120 written out with torch autograd
-(value and gradient), and -- when the reference checkout is present in this container -- against the reference
-classes themselves."""
-import importlib.util
+(value and gradient), and against the values and gradients of the reference classes themselves (tests/golden/distance.npz)."""
 import os
 
 import pytest
@@ -113,32 +111,22 @@ def test_pit_over_negsdr_and_mse_uses_the_generic_path():
     torch.testing.assert_close(loss2, ((x.detach() - t[:, [1, 0]]) ** 2).mean())
 
 
-REF = "/root/reference/src/criterion"
-
-
-def _load_reference(fname, modname):
-    spec = importlib.util.spec_from_file_location(modname, os.path.join(REF, fname))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
-def test_against_reference_classes():
-    rd, rs = _load_reference("distance.py", "_ref_distance"), _load_reference("sdr.py", "_ref_sdr")
-    g = torch.Generator().manual_seed(77)
-    t = torch.randn(3, 4, 2, 333, generator=g, dtype=torch.float64)      # the music recipe's (batch, sources, channels, T)
-    x = t + 0.5 * torch.randn(3, 4, 2, 333, generator=g, dtype=torch.float64)
-    pairs = [(MeanAbsoluteError(dim=-1, reduction="mean"), rd.MeanAbsoluteError(dim=-1, reduction="mean")),
-             (MeanSquaredError(dim=-1, reduction="mean"), rd.MeanSquaredError(dim=-1, reduction="mean")),
-             (MeanSquaredError(dim=(2, 3), reduction="sum"), rd.MeanSquaredError(dim=(2, 3), reduction="sum")),
-             (L1Loss(dim=3), rd.L1Loss(dim=3)), (L2Loss(dim=1, reduction="sum"), rd.L2Loss(dim=1, reduction="sum")),
-             (SDR(), rs.SDR()), (NegSDR(reduction="sum"), rs.NegSDR(reduction="sum"))]
-    for mine, ref in pairs:
+def test_against_reference_classes(golden_dir):
+    """The reference's own criterion classes on the same inputs: their values and input gradients are tests/golden/distance.npz
+    (oracle/make_golden.py::distance_golden)."""
+    import numpy as np
+    from oracle.make_golden import DISTANCE_CASES, distance_inputs
+    fx = np.load(os.path.join(golden_dir, "distance.npz"))
+    x, t = distance_inputs()                                              # the music recipe's (batch, sources, channels, T)
+    mine = {"MeanAbsoluteError": MeanAbsoluteError, "MeanSquaredError": MeanSquaredError, "L1Loss": L1Loss, "L2Loss": L2Loss, "SDR": SDR, "NegSDR": NegSDR}
+    for i, (cls, kw) in enumerate(DISTANCE_CASES):
+        crit = mine[cls](**kw)
+        assert crit.maximize == bool(fx["{}/maximize".format(i)])
         for batch_mean in (True, False):
-            a, b = x.clone().requires_grad_(True), x.clone().requires_grad_(True)
-            la, lb = mine(a, t, batch_mean=batch_mean), ref(b, t, batch_mean=batch_mean)
-            assert la.shape == lb.shape and mine.maximize == ref.maximize
+            a = x.clone().requires_grad_(True)
+            la = crit(a, t, batch_mean=batch_mean)
+            lb, gb = torch.from_numpy(fx["{}/{:d}/value".format(i, batch_mean)]), torch.from_numpy(fx["{}/{:d}/grad".format(i, batch_mean)])
+            assert la.shape == lb.shape
             torch.testing.assert_close(la, lb, rtol=1e-12, atol=1e-12)
-            la.sum().backward(); lb.sum().backward()
-            torch.testing.assert_close(a.grad, b.grad, rtol=2e-7, atol=1e-13)
+            la.sum().backward()
+            torch.testing.assert_close(a.grad, gb, rtol=2e-7, atol=1e-13)

@@ -358,3 +358,28 @@ def test_bench_without_gpu_fails_loudly():
         return
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode != 0 and "no GPU visible" in r.stderr
+
+
+def test_bench_dump_outputs_are_the_same_on_every_run(tmp_path):
+    """`bench.py --dump-outputs DIR` (here the gloo dry run on the CPU emulator): after the timed steps it writes the last step's loss,
+    parameters and gradient buffer as float32 / float64 .npy files, and two runs with the same arguments write the same arrays."""
+    import json
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["SEPK_BENCH_BACKEND"] = "gloo"
+    outs = []
+    for i in range(2):
+        d = str(tmp_path / "run{}".format(i))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
+                            "--dump-outputs", d], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and "detail" not in line
+        outs.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    assert {"gradients", "loss", "parameters"} <= set(outs[0]) <= {"gradients", "loss", "parameters", "pattern"}      # pattern: recorded step
+    assert sum(a.nbytes for a in outs[0].values()) <= 64 * 2 ** 20
+    for name, a in outs[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+        assert np.array_equal(a, outs[1][name]), name
+    assert outs[0]["loss"].reshape(-1)[0] == np.float64(np.float32(line["config"]["final_loss"]))

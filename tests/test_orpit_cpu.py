@@ -2,6 +2,8 @@
 reference model run through the reference driver's own loop (egs/wsj0-mix/orpit_conv-tasnet/src/adhoc_driver.py:193-207),
 and the ORPIT training criterion against the reference's per-item python loop (src/criterion/pit.py:87-161)."""
 import os
+import sys
+import types
 
 import pytest
 import torch
@@ -13,9 +15,35 @@ from models.conv_tasnet import ConvTasNet
 from criterion.sdr import NegSISDR
 from criterion.pit import PIT1d, ORPIT
 from recipes.orpit import ORPITEvaluator, separate_one_and_rest
-from test_oracle_vs_reference_cpu import REF, _reference_classes
 
+REF = "/root/reference/src"
 pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+
+
+def _reference_classes():
+    """The reference's ConvTasNet / criteria, imported from the reference tree under a private module namespace so that this
+    repository's own `models`, `criterion`, ... packages (already imported by other tests) are left alone."""
+    saved = {k: v for k, v in sys.modules.items() if k.split(".")[0] in ("models", "criterion", "modules", "utils", "transforms", "algorithm", "conv", "norm")}
+    for k in saved:
+        del sys.modules[k]
+    stub = "torchaudio" not in sys.modules           # the reference imports it transitively without using it on this path
+    if stub:
+        sys.modules["torchaudio"] = types.ModuleType("torchaudio")
+    path = list(sys.path)
+    sys.path[:] = [REF] + [p for p in path if "dnn-based_source_separation_amd" not in p]
+    try:
+        from models.conv_tasnet import ConvTasNet
+        from criterion.sdr import NegSISDR
+        from criterion.pit import PIT1d
+        assert sys.modules["models.conv_tasnet"].__file__.startswith(REF)
+        return ConvTasNet, NegSISDR, PIT1d
+    finally:
+        sys.path[:] = path
+        if stub:
+            del sys.modules["torchaudio"]
+        for k in [k for k in sys.modules if k.split(".")[0] in ("models", "criterion", "modules", "utils", "transforms", "algorithm", "conv", "norm")]:
+            del sys.modules[k]
+        sys.modules.update(saved)
 
 
 @pytest.fixture()

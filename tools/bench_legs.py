@@ -276,6 +276,32 @@ def furthest_from_roof(by_kernel, n=6, min_share=0.03):
 
 
 # ---- workload constants; restated here so that the timed path imports nothing from oracle/ -------
+DUMP_BUDGET_BYTES = 60 * 10 ** 6         # under 64 MB (either convention) with the .npy headers
+
+
+def dump_outputs(out_dir, tensors, budget=DUMP_BUDGET_BYTES):
+    """bench.py --dump-outputs: every tensor (None entries skipped) as out_dir/<name>.npy, float64 tensors as float64 and the rest as
+    float32.  When they exceed `budget` bytes together, an array beyond its proportional share is replaced by a fixed sample of its
+    flattened entries (seeded index set, sorted: the same entries on every run)."""
+    import numpy as np
+    arrays = {}
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        arrays[name] = np.ascontiguousarray(t.cpu().numpy())
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > budget:
+            keep = int(budget * a.nbytes / total) // a.itemsize
+            if keep < a.size:
+                idx = np.sort(np.random.default_rng(12345).choice(a.size, keep, replace=False))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def num_frames(T, L, S):
     """Encoder frames of a T-sample utterance with ConvTasNet's input padding (reference conv_tasnet.py:145-149)."""
     padding = (S - (T - L) % S) % S
@@ -652,6 +678,7 @@ def bench_dual_path(args):
         opt.step()
         return loss.detach()
     launch = "eager (one launch per kernel)"
+    fused = None
     if args.config == "causal" and os.environ.get("SEPK_TORCH_ADAM", "0") != "1":
         # Conv-TasNet keeps its parameters in one flat buffer: clip + Adam as the headline's step takes them (sepkernels.train.FusedTrainStep:
         # gradients gathered into the flat buffer, one norm kernel, one fused Adam) instead of torch's foreach passes
@@ -671,6 +698,14 @@ def bench_dual_path(args):
         loss = step()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        if fused is not None:                 # the fused step keeps parameters and gradient in its flat buffers
+            flat, gflat = fused.flat, fused.gflat
+        else:
+            params = [q for q in model.parameters() if q.is_floating_point()]
+            flat = torch.cat([q.detach().reshape(-1) for q in params])
+            gflat = torch.cat([(torch.zeros_like(q) if q.grad is None else q.grad).reshape(-1) for q in params])
+        dump_outputs(args.dump_outputs, {"loss": loss.double(), "parameters": flat, "gradients": gflat})
     L, S = cfg["kernel_size"], cfg["stride"]
     F = (T_SAMPLES + (S - (T_SAMPLES - L) % S) % S - L) // S + 1
     config = {"workload": "{}, 2 spk, 4 s @ 8 kHz synthetic mixtures, batch {}{}, fwd + PIT(NegSI-SDR) + bwd + clip(5) + Adam".format(
