@@ -1,0 +1,312 @@
+// Online (chunk-by-chunk) separation of a CAUSAL Conv-TasNet: the kernels that carry state from one chunk of a stream to the next.
+//
+// A causal model (reference src/models/conv_tasnet.py:62, causal=True) uses cumulative layer norm and left padding only, so mask frame f
+// depends on encoder frames <= f (modules/norm.py:58-101, models/tdcn.py:125-132) and output sample tau of the overlap-add is final once
+// every frame with f S <= tau has been seen.  sepkernels/online.py runs a chunk of n frames of every stream as ONE pass over stream-major
+// columns -- column j = stream * n + frame of a (C, ldt) matrix, so that each 1x1 product of a layer is one sep_pw_gemm over all streams --
+// and these kernels are the pieces of that pass that look back in time:
+//   sep_online_encoder_fwd    analysis convolution of [carry | chunk] (filterbank.py:205-235), new carry -> carry_next
+//   sep_online_cln_fwd        [PReLU ->] cLN with the fp64 running sums {sum x, sum x^2} of every stream carried in device memory
+//   sep_online_depthwise_fwd  causal dilated depthwise taps over [history | chunk], the history of (P - 1) d frames kept in time order
+//   sep_online_decoder_fwd    mask * w, synthesis and overlap-add into [tail | n S]: n S final samples, new tail -> tail_next
+//   sep_online_advance        frame counters += n, carry <- carry_next, tail <- tail_next (the last launch of a chunk)
+//   sep_online_reset          zero the state of the streams a device mask selects
+// Everything that changes from chunk to chunk (frame counters, running sums, histories, carries, tails) lives in device memory, so a
+// recorded chunk step (sep_run_sequence) replays correctly.  No atomics: every result is formed in a fixed order, replays are bitwise.
+// State that is read and written by the same launch is owned by ONE workgroup that reads before a barrier and writes after it (cLN sums,
+// depthwise histories); the encoder carry and the decoder tail are read by many workgroups and therefore written to a second buffer that
+// sep_online_advance copies back.
+#include "common.hpp"
+
+namespace {
+
+// w[nb][s n + f] = [ReLU] sum_k E[nb][k] ext_s[f S + k], ext_s = [carry_s (L - S) | chunk_s (n S)];  columns [num_streams n, ldt) = 0.
+// carry_next_s = ext_s[n S .. n S + L - S).
+__global__ __launch_bounds__(256) void online_encoder_kernel(const float* __restrict__ chunk, const float* __restrict__ E, const float* __restrict__ carry,
+                                                             float* __restrict__ carry_next, float* __restrict__ w, int num_streams, int L, int S, int n,
+                                                             int ldt, int relu) {
+    const int nb = blockIdx.y;
+    const int col = blockIdx.x * 256 + threadIdx.x;
+    const int keep = L - S;
+    const int64_t span = (int64_t)n * S;
+    const int cols = num_streams * n;
+    if (col < ldt) {
+        float acc = 0.f;
+        if (col < cols) {
+            const int s = col / n, f = col - s * n;
+            const float* cs = carry + (size_t)s * keep;
+            const float* xs = chunk + (size_t)s * span;
+            const float* e = E + (size_t)nb * L;
+            for (int k = 0; k < L; ++k) {
+                const int i = f * S + k;
+                const float v = i < keep ? cs[i] : xs[i - keep];
+                acc = fmaf(e[k], v, acc);
+            }
+            if (relu) acc = fmaxf(acc, 0.f);
+        }
+        w[(size_t)nb * ldt + col] = acc;
+    }
+    if (nb == 0 && keep > 0) {
+        for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < (int64_t)num_streams * keep; g += (int64_t)gridDim.x * 256) {
+            const int s = (int)(g / keep), i = (int)(g - (int64_t)s * keep);
+            const int64_t e = span + i;                                   // index into ext_s
+            carry_next[g] = e < keep ? carry[(size_t)s * keep + e] : chunk[(size_t)s * span + (e - keep)];
+        }
+    }
+}
+
+constexpr int OC_TW = 32;         // frames per tile of the cLN pass
+constexpr int OC_CG = 8;          // channel groups: 8 x 32 = 256 threads
+
+// One workgroup per stream: tiles of 32 frames, column sums over the channels (fp32 per channel group -> fp64), an inclusive fp64 scan
+// over the tile on top of the running sums of everything the stream has seen, then the apply pass over the tile.  count = C (t + 1) with t
+// the absolute frame index (frames[s] + f).  The running sums are read by wave 0 at the start and written by lane 0 after the last barrier.
+__global__ __launch_bounds__(256) void online_cln_kernel(const float* __restrict__ x, const float* __restrict__ alpha, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, float* __restrict__ y, double* __restrict__ sums, int sums_stride,
+                                                         const int64_t* __restrict__ frames, int C, int n, int ldt, float eps) {
+    __shared__ float red[2][OC_CG][OC_TW];
+    __shared__ float mr[2][OC_TW];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int fl = tid & (OC_TW - 1), cg = tid / OC_TW;
+    const bool act = alpha != nullptr;
+    const float al = act ? alpha[0] : 1.f;
+    const size_t col0 = (size_t)s * n;
+    double* sm = sums + (size_t)s * sums_stride;
+    double ca = 0.0, cq = 0.0, t0 = 0.0;
+    if (tid < 64) {
+        ca = sm[0];
+        cq = sm[1];
+        t0 = (double)frames[s];
+    }
+    for (int f0 = 0; f0 < n; f0 += OC_TW) {
+        const int f = f0 + fl;
+        float s1 = 0.f, s2 = 0.f;
+        if (f < n) {
+            for (int c = cg; c < C; c += OC_CG) {
+                float u = x[(size_t)c * ldt + col0 + f];
+                if (act) u = prelu_f(u, al);
+                s1 += u;
+                s2 = fmaf(u, u, s2);
+            }
+        }
+        red[0][cg][fl] = s1;
+        red[1][cg][fl] = s2;
+        __syncthreads();
+        if (tid < 64) {
+            double a = 0.0, q = 0.0;
+            if (tid < OC_TW) {
+#pragma unroll
+                for (int g = 0; g < OC_CG; ++g) { a += (double)red[0][g][tid]; q += (double)red[1][g][tid]; }
+            }
+#pragma unroll
+            for (int off = 1; off < OC_TW; off <<= 1) {                 // inclusive prefix over the tile's frames (lanes 32 .. 63 carry zeros)
+                const double ua = __shfl_up(a, off, 64), uq = __shfl_up(q, off, 64);
+                if (tid >= off) { a += ua; q += uq; }
+            }
+            const double ta = __shfl(a, OC_TW - 1, 64), tq = __shfl(q, OC_TW - 1, 64);
+            if (tid < OC_TW) {
+                float mf = 0.f, rf = 0.f;
+                if (f0 + tid < n) {
+                    const double cnt = (double)C * (t0 + (double)(f0 + tid) + 1.0);
+                    const double m = (ca + a) / cnt;
+                    double var = (cq + q) / cnt - m * m;
+                    if (var < 0.0) var = 0.0;
+                    mf = (float)m;
+                    rf = (float)(1.0 / (sqrt(var) + (double)eps));
+                }
+                mr[0][tid] = mf;
+                mr[1][tid] = rf;
+            }
+            ca += ta;
+            cq += tq;
+        }
+        __syncthreads();
+        const int nf = n - f0 < OC_TW ? n - f0 : OC_TW;
+        for (int e = tid; e < C * OC_TW; e += 256) {
+            const int c = e / OC_TW, j = e - c * OC_TW;
+            if (j >= nf) continue;
+            const size_t idx = (size_t)c * ldt + col0 + f0 + j;
+            float u = x[idx];
+            if (act) u = prelu_f(u, al);
+            y[idx] = (u - mr[0][j]) * mr[1][j] * gamma[c] + beta[c];
+        }
+        __syncthreads();                                                  // red / mr are rewritten by the next tile
+    }
+    if (s == (int)gridDim.x - 1) {                                        // the pad columns [num_streams n, ldt) of every row
+        const int cols = (int)gridDim.x * n, pad = ldt - cols;
+        for (int64_t e = tid; e < (int64_t)C * pad; e += 256) {
+            const int c = (int)(e / pad), j = (int)(e - (int64_t)c * pad);
+            y[(size_t)c * ldt + cols + j] = 0.f;
+        }
+    }
+    if (tid == 0) {
+        sm[0] = ca;
+        sm[1] = cq;
+    }
+}
+
+// One workgroup per (channel, stream) row: the history is copied to LDS before the barrier, outputs and the new history are formed after
+// it from the LDS copy and the (unmodified) input, so a chunk shorter than the history (n < (P - 1) d) cannot race with itself.
+// y[f] = bias + sum_k w[k] ext[f + k d], ext = [history ((P - 1) d) | x (n)];  new history = ext[n .. n + (P - 1) d).
+__global__ __launch_bounds__(256) void online_depthwise_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                               float* __restrict__ ring, int64_t ring_stride, float* __restrict__ y, int n, int ldt, int P, int d) {
+    extern __shared__ float hist[];
+    const int c = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
+    const int D = (P - 1) * d;
+    float* rg = ring + (size_t)s * ring_stride + (size_t)c * D;
+    const float* xr = x + (size_t)c * ldt + (size_t)s * n;
+    float* yr = y + (size_t)c * ldt + (size_t)s * n;
+    for (int i = tid; i < D; i += 256) hist[i] = rg[i];
+    __syncthreads();
+    const float b = bias ? bias[c] : 0.f;
+    const float* wc = w + (size_t)c * P;
+    for (int f = tid; f < n; f += 256) {
+        float acc = b;
+        for (int k = 0; k < P; ++k) {
+            const int e = f + k * d;
+            acc = fmaf(wc[k], e < D ? hist[e] : xr[e - D], acc);
+        }
+        yr[f] = acc;
+    }
+    for (int i = tid; i < D; i += 256) {
+        const int e = n + i;
+        rg[i] = e < D ? hist[e] : xr[e - D];
+    }
+    if (s == (int)gridDim.y - 1)
+        for (int t = (int)gridDim.y * n + tid; t < ldt; t += 256) y[(size_t)c * ldt + t] = 0.f;
+}
+
+// Thread per output sample i of [0, n S + L - S) of (stream, source): the old tail plus the overlap-add of the frames that cover i
+// (f S <= i < f S + L), latent = w * mask.  i < n S goes to out, the rest to tail_next.
+__global__ __launch_bounds__(256) void online_decoder_kernel(const float* __restrict__ w, const float* __restrict__ mask, const float* __restrict__ Dm,
+                                                             const float* __restrict__ tail, float* __restrict__ tail_next, float* __restrict__ out,
+                                                             int n_src, int N, int L, int S, int n, int ldt) {
+    const int src = blockIdx.y, s = blockIdx.z;
+    const int keep = L - S;
+    const int span = n * S;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= span + keep) return;
+    const size_t row = (size_t)s * n_src + src;
+    float acc = i < keep ? tail[row * keep + i] : 0.f;
+    const int f_hi = (i / S) < n - 1 ? (i / S) : n - 1;
+    const int f_lo = i - L + 1 > 0 ? (i - L + S) / S : 0;
+    for (int f = f_lo; f <= f_hi; ++f) {
+        const int k = i - f * S;
+        const size_t col = (size_t)s * n + f;
+        for (int nb = 0; nb < N; ++nb) {
+            const float lat = w[(size_t)nb * ldt + col] * mask[((size_t)src * N + nb) * ldt + col];
+            acc = fmaf(lat, Dm[(size_t)nb * L + k], acc);
+        }
+    }
+    if (i < span) out[row * span + i] = acc;
+    else tail_next[row * keep + (i - span)] = acc;
+}
+
+__global__ __launch_bounds__(256) void online_advance_kernel(int64_t* __restrict__ frames, float* __restrict__ carry, const float* __restrict__ carry_next,
+                                                             int64_t carry_total, float* __restrict__ tail, const float* __restrict__ tail_next,
+                                                             int64_t tail_total, int num_streams, int n) {
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < carry_total || g < tail_total || g < num_streams; g += (int64_t)gridDim.x * 256) {
+        if (g < num_streams) frames[g] += n;
+        if (g < carry_total) carry[g] = carry_next[g];
+        if (g < tail_total) tail[g] = tail_next[g];
+    }
+}
+
+// grid (G, num_streams): the workgroups of a selected stream zero its slice of every state buffer
+__global__ __launch_bounds__(256) void online_reset_kernel(const uint8_t* __restrict__ mask, int64_t* __restrict__ frames, float* __restrict__ carry,
+                                                           int carry_len, double* __restrict__ sums, int sums_len, float* __restrict__ rings,
+                                                           int64_t rings_len, float* __restrict__ tail, int tail_len) {
+    const int s = blockIdx.y;
+    if (!mask[s]) return;
+    const int64_t g0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if (g0 == 0) frames[s] = 0;
+    for (int64_t g = g0; g < carry_len; g += step) carry[(size_t)s * carry_len + g] = 0.f;
+    for (int64_t g = g0; g < sums_len; g += step) sums[(size_t)s * sums_len + g] = 0.0;
+    for (int64_t g = g0; g < rings_len; g += step) rings[(size_t)s * rings_len + g] = 0.f;
+    for (int64_t g = g0; g < tail_len; g += step) tail[(size_t)s * tail_len + g] = 0.f;
+}
+
+inline int ceil_div_i(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+}  // namespace
+
+extern "C" int sep_online_encoder_fwd(const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N,
+                                      int L, int S, int n, int ldt, int relu, sep_stream_t stream) {
+    SEP_REQUIRE(chunk && E && w && num_streams > 0 && N > 0 && S > 0 && L >= S && L % S == 0 && n > 0, "sep_online_encoder_fwd: bad arguments");
+    SEP_REQUIRE((carry && carry_next) || L == S, "sep_online_encoder_fwd: carry buffers missing");
+    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0 && N <= 65535, "sep_online_encoder_fwd: bad sizes (streams=%d n=%d ldt=%d N=%d)",
+                num_streams, n, ldt, N);
+    hipLaunchKernelGGL(online_encoder_kernel, dim3(ceil_div_i(ldt, 256), N), dim3(256), 0, (hipStream_t)stream, chunk, E, carry, carry_next, w,
+                       num_streams, L, S, n, ldt, relu);
+    SEP_CHECK_LAUNCH("sep_online_encoder_fwd");
+    return 0;
+}
+
+extern "C" int sep_online_cln_fwd(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums, int sums_stride,
+                                  const int64_t* frames, int num_streams, int C, int n, int ldt, float eps, sep_stream_t stream) {
+    SEP_REQUIRE(x && gamma && beta && y && sums && frames && num_streams > 0 && C > 0 && n > 0 && sums_stride >= 2, "sep_online_cln_fwd: bad arguments");
+    SEP_REQUIRE(x != y, "sep_online_cln_fwd: y may not alias x");
+    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0, "sep_online_cln_fwd: bad sizes (streams=%d n=%d ldt=%d)", num_streams, n, ldt);
+    hipLaunchKernelGGL(online_cln_kernel, dim3(num_streams), dim3(256), 0, (hipStream_t)stream, x, alpha, gamma, beta, y, sums, sums_stride, frames,
+                       C, n, ldt, eps);
+    SEP_CHECK_LAUNCH("sep_online_cln_fwd");
+    return 0;
+}
+
+extern "C" int sep_online_depthwise_fwd(const float* x, const float* w, const float* bias, float* ring, int64_t ring_stride, float* y, int num_streams,
+                                        int C, int n, int ldt, int P, int dilation, sep_stream_t stream) {
+    SEP_REQUIRE(x && w && ring && y && x != y && num_streams > 0 && num_streams <= 65535 && C > 0 && n > 0 && P >= 2 && dilation > 0,
+                "sep_online_depthwise_fwd: bad arguments");
+    const int64_t D = (int64_t)(P - 1) * dilation;
+    SEP_REQUIRE(D <= 16384, "sep_online_depthwise_fwd: history of %lld frames exceeds LDS", (long long)D);
+    SEP_REQUIRE(ring_stride >= (int64_t)C * D, "sep_online_depthwise_fwd: ring_stride %lld < C (P - 1) d", (long long)ring_stride);
+    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0, "sep_online_depthwise_fwd: bad sizes (streams=%d n=%d ldt=%d)", num_streams, n, ldt);
+    hipLaunchKernelGGL(online_depthwise_kernel, dim3(C, num_streams), dim3(256), (size_t)D * sizeof(float), (hipStream_t)stream, x, w, bias, ring,
+                       ring_stride, y, n, ldt, P, dilation);
+    SEP_CHECK_LAUNCH("sep_online_depthwise_fwd");
+    return 0;
+}
+
+extern "C" int sep_online_decoder_fwd(const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out, int num_streams,
+                                      int n_src, int N, int L, int S, int n, int ldt, sep_stream_t stream) {
+    SEP_REQUIRE(w && mask && D && out && num_streams > 0 && num_streams <= 65535 && n_src > 0 && n_src <= 65535 && N > 0 && S > 0 && L >= S &&
+                L % S == 0 && n > 0, "sep_online_decoder_fwd: bad arguments");
+    SEP_REQUIRE((tail && tail_next) || L == S, "sep_online_decoder_fwd: tail buffers missing");
+    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0, "sep_online_decoder_fwd: bad sizes (streams=%d n=%d ldt=%d)", num_streams, n, ldt);
+    hipLaunchKernelGGL(online_decoder_kernel, dim3(ceil_div_i((int64_t)n * S + L - S, 256), n_src, num_streams), dim3(256), 0, (hipStream_t)stream, w, mask,
+                       D, tail, tail_next, out, n_src, N, L, S, n, ldt);
+    SEP_CHECK_LAUNCH("sep_online_decoder_fwd");
+    return 0;
+}
+
+extern "C" int sep_online_advance(int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next,
+                                  int tail_len, int num_streams, int n, sep_stream_t stream) {
+    SEP_REQUIRE(frames && num_streams > 0 && n > 0 && carry_len >= 0 && tail_len >= 0, "sep_online_advance: bad arguments");
+    SEP_REQUIRE((carry && carry_next) || carry_len == 0, "sep_online_advance: carry buffers missing");
+    SEP_REQUIRE((tail && tail_next) || tail_len == 0, "sep_online_advance: tail buffers missing");
+    const int64_t ct = (int64_t)num_streams * carry_len, tt = (int64_t)num_streams * tail_len;
+    int64_t most = ct > tt ? ct : tt;
+    most = most > num_streams ? most : num_streams;
+    const int grid = ceil_div_i(most, 256) > 1024 ? 1024 : ceil_div_i(most, 256);
+    hipLaunchKernelGGL(online_advance_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, carry, carry_next, ct, tail, tail_next, tt,
+                       num_streams, n);
+    SEP_CHECK_LAUNCH("sep_online_advance");
+    return 0;
+}
+
+extern "C" int sep_online_reset(const uint8_t* mask, int num_streams, int64_t* frames, float* carry, int carry_len, double* sums, int sums_len,
+                                float* rings, int64_t rings_len, float* tail, int tail_len, sep_stream_t stream) {
+    SEP_REQUIRE(mask && frames && num_streams > 0 && num_streams <= 65535 && carry_len >= 0 && sums_len >= 0 && rings_len >= 0 && tail_len >= 0,
+                "sep_online_reset: bad arguments");
+    SEP_REQUIRE((carry || carry_len == 0) && (sums || sums_len == 0) && (rings || rings_len == 0) && (tail || tail_len == 0),
+                "sep_online_reset: state buffer missing");
+    int64_t most = rings_len;
+    if (carry_len > most) most = carry_len;
+    if (sums_len > most) most = sums_len;
+    if (tail_len > most) most = tail_len;
+    const int g = ceil_div_i(most < 1 ? 1 : most, 256);
+    hipLaunchKernelGGL(online_reset_kernel, dim3(g > 256 ? 256 : g, num_streams), dim3(256), 0, (hipStream_t)stream, mask, frames, carry, carry_len,
+                       sums, sums_len, rings, rings_len, tail, tail_len);
+    SEP_CHECK_LAUNCH("sep_online_reset");
+    return 0;
+}

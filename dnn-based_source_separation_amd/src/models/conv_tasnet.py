@@ -444,6 +444,16 @@ class ConvTasNet(nn.Module):
             return est, latent[..., :F_]
         return out, None
 
+    def online_separator(self, num_streams=1, chunk_size=None, record=True):
+        """A sepkernels.online.OnlineSeparator: chunk-by-chunk separation of `num_streams` mono streams by this CAUSAL model, with an algorithmic
+        delay of L - S samples.  Chunks are (num_streams, 1, k * stride) on the model's device; each returns (num_streams, n_sources, k * stride);
+        flush() returns the last L - S samples and resets.  Concatenated, the outputs equal model(F.pad(x, (L - S, 0))) for an input x whose
+        length is a multiple of the stride.  The first chunk of `chunk_size` samples (default: the first chunk's size) is recorded and replayed
+        by one sep_run_sequence call afterwards (record=False: every chunk is launched eagerly).  Refuses non-causal models (ValueError: gLN
+        needs the whole signal), causal models outside the staged family (NotImplementedError with `staged_reason`) and in_channels != 1."""
+        from sepkernels.online import OnlineSeparator
+        return OnlineSeparator(self, num_streams=num_streams, chunk_size=chunk_size, record=record)
+
     def _run_composed(self, mixture, want_latent):
         """The reference's own sequence (conv_tasnet.py:121-171) on this repository's modules, for configurations outside
         the fused family: pad -> encoder -> separator -> mask * w -> decoder (transposed convolution = overlap-add) -> crop.

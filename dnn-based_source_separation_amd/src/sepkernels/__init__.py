@@ -191,6 +191,13 @@ SIGNATURES = {
     "sep_pit_finish": [_vp, _vp, _vp, _I, _I, _I, _F, _F, _vp, _vp, _vp, _vp],
     "sep_axpby": [_vp, _F, _vp, _F, _vp, _L, _vp],
     "sep_split_rows": [_vp, _vp, _vp, _vp, _I, _I, _I, _I, _I, _vp],
+    # online separation of a causal Conv-TasNet (ABI 23, additive): sepkernels/online.py
+    "sep_online_encoder_fwd": [_vp] * 5 + [_I] * 7 + [_vp],
+    "sep_online_cln_fwd": [_vp] * 6 + [_I, _vp] + [_I] * 4 + [_F, _vp],
+    "sep_online_depthwise_fwd": [_vp] * 4 + [_L, _vp] + [_I] * 6 + [_vp],
+    "sep_online_decoder_fwd": [_vp] * 6 + [_I] * 7 + [_vp],
+    "sep_online_advance": [_vp] * 3 + [_I] + [_vp] * 2 + [_I] * 3 + [_vp],
+    "sep_online_reset": [_vp, _I, _vp, _vp, _I, _vp, _I, _vp, _L, _vp, _I, _vp],
 }
 _RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
              "sep_gln_tokens_ws_bytes": ctypes.c_size_t}
@@ -374,6 +381,7 @@ class HipBackend:
     arithmetic so that the host-side orchestration can be exercised without a GPU (test infrastructure only)."""
 
     name = "hip"
+    records = True      # every launch goes through the library handle: sepkernels.recording() can capture it (the CPU emulator's cannot)
 
     def pw_gemm(self, *, B, M, K, T, ldt, A, X, Y, trans_a=0, A2=None, X2=None, k_split=0, Y2=None, m_split=0,
                 pro_mode=PRO_NONE, epi_flags=0, accumulate=0, eps=1e-12, count=0.0, bias=None, pro_alpha=None,
@@ -713,6 +721,31 @@ class HipBackend:
     def adam_step_dev(self, p, g, m, v, sqnorm, n, lr_dev, step_dev, beta1, beta2, eps, weight_decay, max_norm, grad_scale):
         _check(load().sep_adam_step_dev(_ptr(p, _f32), _ptr(g, _f32), _ptr(m, _f32), _ptr(v, _f32), _ptr(sqnorm, _f64), n, _ptr(lr_dev, _f32),
                                         _ptr(step_dev, torch.int32), beta1, beta2, eps, weight_decay, max_norm, grad_scale, _stream()), "sep_adam_step_dev")
+
+    # ---- online separation of a causal Conv-TasNet (sepkernels/online.py; include/sepkernels.h, ABI 23 additive) ----
+    def online_encoder_fwd(self, chunk, E, carry, carry_next, w, num_streams, N, L, S, n, ldt, relu):
+        _check(load().sep_online_encoder_fwd(_ptr(chunk, _f32), _ptr(E, _f32), _ptr(carry, _f32), _ptr(carry_next, _f32), _ptr(w, _f32), num_streams,
+                                             N, L, S, n, ldt, int(relu), _stream()), "sep_online_encoder_fwd")
+
+    def online_cln_fwd(self, x, alpha, gamma, beta, y, sums, sums_stride, frames, num_streams, C, n, ldt, eps):
+        _check(load().sep_online_cln_fwd(_ptr(x, _f32), _ptr(alpha, _f32), _ptr(gamma, _f32), _ptr(beta, _f32), _ptr(y, _f32), _ptr(sums, _f64),
+                                         sums_stride, _ptr(frames, torch.int64), num_streams, C, n, ldt, eps, _stream()), "sep_online_cln_fwd")
+
+    def online_depthwise_fwd(self, x, w, bias, ring, ring_stride, y, num_streams, C, n, ldt, P, dilation):
+        _check(load().sep_online_depthwise_fwd(_ptr(x, _f32), _ptr(w, _f32), _ptr(bias, _f32), _ptr(ring, _f32), ring_stride, _ptr(y, _f32),
+                                               num_streams, C, n, ldt, P, dilation, _stream()), "sep_online_depthwise_fwd")
+
+    def online_decoder_fwd(self, w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n, ldt):
+        _check(load().sep_online_decoder_fwd(_ptr(w, _f32), _ptr(mask, _f32), _ptr(D, _f32), _ptr(tail, _f32), _ptr(tail_next, _f32), _ptr(out, _f32),
+                                             num_streams, n_src, N, L, S, n, ldt, _stream()), "sep_online_decoder_fwd")
+
+    def online_advance(self, frames, carry, carry_next, carry_len, tail, tail_next, tail_len, num_streams, n):
+        _check(load().sep_online_advance(_ptr(frames, torch.int64), _ptr(carry, _f32), _ptr(carry_next, _f32), carry_len, _ptr(tail, _f32),
+                                         _ptr(tail_next, _f32), tail_len, num_streams, n, _stream()), "sep_online_advance")
+
+    def online_reset(self, mask, num_streams, frames, carry, carry_len, sums, sums_len, rings, rings_len, tail, tail_len):
+        _check(load().sep_online_reset(_ptr(mask, torch.uint8), num_streams, _ptr(frames, torch.int64), _ptr(carry, _f32), carry_len, _ptr(sums, _f64),
+                                       sums_len, _ptr(rings, _f32), rings_len, _ptr(tail, _f32), tail_len, _stream()), "sep_online_reset")
 
 
 _backend = HipBackend()

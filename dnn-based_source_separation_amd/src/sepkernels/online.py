@@ -1,0 +1,242 @@
+"""
+Online (chunk-by-chunk) separation of a CAUSAL Conv-TasNet: audio goes in as it arrives, separated audio comes out L - S samples later.
+
+    sep = model.online_separator(num_streams=64, chunk_size=80)
+    for chunk in chunks:                 # (num_streams, 1, k S) on the model's device
+        y = sep(chunk)                   # (num_streams, n_sources, k S)
+    tail = sep.flush()                   # (num_streams, n_sources, L - S), then every stream starts over
+
+Contract (L = kernel_size, S = stride): a stream starts with L - S zero samples of pre-roll; every chunk of n S samples yields n encoder frames
+and exactly n S output samples per source; flush() returns the last L - S samples.  For a mono input x of length m (a multiple of S)
+
+    torch.cat([sep(c) for c in chunks] + [sep.flush()], -1) == model(F.pad(x, (L - S, 0)))
+
+and the separated version of x[t] is output sample t + L - S (algorithmic delay L - S samples).  It holds because a causal model's mask frame f
+depends on encoder frames <= f only -- cLN is cumulative (reference src/modules/norm.py:42-101), the depthwise taps are left-padded by (P - 1) d
+(src/models/tdcn.py:125-132) -- and output sample tau receives overlap-add from the frames f with f S <= tau < f S + L only.
+
+A chunk step is net.py-style orchestration: backend calls only, no autograd and no torch kernel between the launches of a chunk.  Every stream's
+n frames are columns stream * n + frame of one (C, ldt) matrix ("stream-major"), so each 1x1 product of a layer is ONE sep_pw_gemm over all
+streams; the state that carries from chunk to chunk (encoder carry, frame counters, the cLN running sums, the depthwise histories, the
+overlap-add tail) lives in device memory and is read by the kernels of csrc/online.hip.  The first chunk of `chunk_size` samples is recorded
+(sepkernels.recording) and later chunks of that size replay it with one sep_run_sequence call; other sizes run the same launches eagerly on
+workspaces cached per size.  No gradients: training is out of scope.
+"""
+import torch
+
+import sepkernels
+from . import backend, EPI_RESIDUAL, EPI_SIGMOID, PRO_PRELU
+from . import net as _net
+
+
+def _round_up(a, b):
+    return (a + b - 1) // b * b
+
+
+class _Workspace:
+    """the activations of one chunk size (n frames per stream): (C, ldt) stream-major matrices, columns [num_streams n, ldt) zero"""
+
+    def __init__(self, sep, n):
+        f = dict(device=sep.device, dtype=sep.dtype)
+        Bs, H, Bn, Sc, N = sep.num_streams, sep.H, sep.Bn, sep.Sc, sep.N
+        self.n = n
+        self.ldt = ldt = _round_up(Bs * n, 128)
+        self.chunk = torch.zeros(Bs, n * sep.S, **f)
+        self.w = torch.zeros(N, ldt, **f)
+        self.wn = torch.zeros(N, ldt, **f)
+        self.xa, self.xb = torch.zeros(Bn, ldt, **f), torch.zeros(Bn, ldt, **f)
+        self.ha, self.hb = torch.zeros(H, ldt, **f), torch.zeros(H, ldt, **f)
+        self.total = torch.zeros(Sc, ldt, **f)
+        self.m = torch.zeros(sep.n_src * N, ldt, **f)
+        self.out = torch.zeros(Bs, sep.n_src, n * sep.S, **f)
+        self.amax = torch.zeros(1, **f)
+
+
+class OnlineSeparator:
+    """Chunk-by-chunk separation of `num_streams` independent mono streams by a causal Conv-TasNet (see the module docstring for the contract).
+    Built by ConvTasNet.online_separator; reads the model's live parameters at every chunk (an in-place update or load_state_dict is seen at
+    the next chunk; after model.to() moved the flat parameter buffer the recording is dropped and made again).
+
+    delay        L - S: output sample t + delay is the separated version of input sample t
+    state_bytes  device memory of the per-stream state (carry, frame counter, cLN sums, depthwise histories, overlap-add tail)"""
+
+    def __init__(self, model, num_streams=1, chunk_size=None, record=True):
+        if not model.causal:
+            raise ValueError("online separation needs a causal model: gLN (causal=False) normalises over the whole signal, which has not arrived yet")
+        if not model.staged:
+            raise NotImplementedError("online separation runs the staged causal family only; this model is outside it: {}".format(model.staged_reason))
+        if model.in_channels != 1:
+            raise NotImplementedError("online separation takes mono streams (in_channels=1), the model has in_channels={}".format(model.in_channels))
+        if num_streams < 1:
+            raise ValueError("num_streams must be >= 1")
+        K = backend()
+        flat = model.flat_parameters()
+        if flat is None:
+            raise RuntimeError("online separation needs the model's parameters co-located in its flat buffer")
+        if K.name == "hip" and (not flat.is_cuda or flat.dtype != torch.float32):
+            raise RuntimeError("online separation runs on the GPU in fp32: move the model to 'cuda' (parameters are {} {})".format(flat.device, flat.dtype))
+        self.model = model
+        self.device, self.dtype = flat.device, flat.dtype
+        self.num_streams = num_streams
+        self.L, self.S = model.kernel_size, model.stride
+        self.delay = self.L - self.S
+        if chunk_size is not None and (chunk_size <= 0 or chunk_size % self.S):
+            raise ValueError("chunk_size must be a positive multiple of the stride {} (got {})".format(self.S, chunk_size))
+        self.chunk_size = chunk_size
+        self.record = bool(record) and getattr(K, "records", False)
+        sep = model.separator
+        self.N, self.n_src = model.n_basis, model.n_sources
+        self.Bn, self.Sc = model.sep_bottleneck_channels, model.sep_skip_channels
+        self.H = model.sep_hidden_channels
+        self.layers = [layer for block in sep.tdcn.net for layer in block.net]
+        self.n_norms = 1 + 2 * len(self.layers)
+        self.ring_offsets, off = [], 0
+        for layer in self.layers:
+            self.ring_offsets.append(off)
+            off += self.H * (layer.kernel_size - 1) * layer.dilation
+        self.ring_len = off
+        f = dict(device=self.device, dtype=self.dtype)
+        Bs, keep = num_streams, self.delay
+        self.frames = torch.zeros(Bs, device=self.device, dtype=torch.int64)
+        self.carry, self.carry_next = torch.zeros(Bs, keep, **f), torch.zeros(Bs, keep, **f)
+        self.sums = torch.zeros(Bs, 2 * self.n_norms, device=self.device, dtype=torch.float64)
+        self.rings = torch.zeros(Bs, self.ring_len, **f)
+        self.tail, self.tail_next = torch.zeros(Bs, self.n_src, keep, **f), torch.zeros(Bs, self.n_src, keep, **f)
+        self.state_bytes = sum(t.numel() * t.element_size() for t in (self.frames, self.carry, self.carry_next, self.sums, self.rings, self.tail,
+                                                                       self.tail_next))
+        self._ws = {}
+        self._seq = self._seq_n = self._seq_flat = None
+
+    # ------------------------------------------------------------------ public
+    def __call__(self, chunk):
+        n = self._check_chunk(chunk)
+        with torch.no_grad():
+            ws = self._ws.get(n)
+            if ws is None:
+                ws = self._ws[n] = _Workspace(self, n)
+            ws.chunk.copy_(chunk.reshape(self.num_streams, n * self.S))
+            target = self.chunk_size if self.chunk_size is not None else n * self.S
+            if self.chunk_size is None:
+                self.chunk_size = target
+            if self.record and n * self.S == target:
+                flat = self.model.flat_parameters()
+                if self._seq is not None and self._seq_flat is not flat:       # model.to() since the recording: its pointers are stale
+                    self._seq = None
+                if self._seq is None:
+                    seq = sepkernels.Sequence()
+                    with sepkernels.recording(seq):
+                        self._step(ws, n)
+                    self._seq, self._seq_n, self._seq_flat = seq, n, flat
+                else:
+                    self._seq.run()
+            else:
+                self._step(ws, n)
+            return ws.out.clone()
+
+    def flush(self):
+        """the last L - S samples of every stream (num_streams, n_sources, L - S); then every stream is reset"""
+        with torch.no_grad():
+            out = self.tail.clone()
+        self.reset()
+        return out
+
+    def reset(self, streams=None):
+        """zero the state of the selected streams (None: all; a list of indices; a bool mask of num_streams); the others are untouched"""
+        Bs = self.num_streams
+        if streams is None:
+            sel = torch.ones(Bs, dtype=torch.uint8)
+        elif torch.is_tensor(streams) and streams.dtype == torch.bool:
+            if streams.numel() != Bs:
+                raise ValueError("the stream mask has {} entries, the separator has {} streams".format(streams.numel(), Bs))
+            sel = streams.reshape(-1).cpu().to(torch.uint8)
+        else:
+            idx = [int(i) for i in (streams.tolist() if torch.is_tensor(streams) else streams)]
+            if any(i < 0 or i >= Bs for i in idx):
+                raise ValueError("stream index out of range 0 .. {}".format(Bs - 1))
+            sel = torch.zeros(Bs, dtype=torch.uint8)
+            sel[idx] = 1
+        mask = sel.to(self.device)
+        keep = self.delay
+        with torch.no_grad():
+            backend().online_reset(mask, Bs, self.frames, self.carry if keep else None, keep, self.sums, 2 * self.n_norms,
+                                   self.rings if self.ring_len else None, self.ring_len, self.tail if keep else None, self.n_src * keep)
+
+    # ------------------------------------------------------------------ the chunk step
+    def _check_chunk(self, chunk):
+        if not torch.is_tensor(chunk) or chunk.dim() != 3 or chunk.shape[0] != self.num_streams or chunk.shape[1] != 1:
+            raise ValueError("a chunk is (num_streams={}, 1, k*{}) (got {})".format(self.num_streams, self.S, tuple(getattr(chunk, "shape", ()))))
+        T = chunk.shape[-1]
+        if T == 0 or T % self.S:
+            raise ValueError("a chunk's length must be a positive multiple of the stride {} (got {})".format(self.S, T))
+        if backend().name == "hip" and not chunk.is_cuda:
+            raise RuntimeError("online separation runs on the GPU: the chunk is a {} tensor".format(chunk.device))
+        if chunk.device != self.device or chunk.dtype != self.dtype:
+            raise ValueError("the chunk must be on {} in {} like the separator's state (got {} {})".format(self.device, self.dtype, chunk.device, chunk.dtype))
+        return T // self.S
+
+    def _step(self, ws, n):
+        """one chunk of n frames of every stream: ~5 launches per TCN layer plus encoder, norm, bottleneck, mask, decoder and advance"""
+        K = backend()
+        model, sep = self.model, self.model.separator
+        Bs, L, S, N, H, Bn, Sc, n_src = self.num_streams, self.L, self.S, self.N, self.H, self.Bn, self.Sc, self.n_src
+        T, ldt = Bs * n, ws.ldt
+        keep = self.delay
+        sums, sstride = self.sums.view(-1), 2 * self.n_norms
+        amax = None
+        if sepkernels.gemm_arith() == sepkernels.ARITH_F16X3 and hasattr(K, "absmax"):
+            flat = model.flat_parameters()
+            K.absmax(flat, ws.amax, flat.numel())            # the operand bound of the chunk's products (alignment gaps of the buffer hold zeros)
+            amax = ws.amax
+
+        def cln(x, y, norm, alpha, i):
+            K.online_cln_fwd(x, alpha, norm.gamma.reshape(-1), norm.beta.reshape(-1), y, sums[2 * i:], sstride, self.frames, Bs, x.shape[0], n, ldt,
+                             norm.eps)
+
+        K.online_encoder_fwd(ws.chunk, model.encoder.conv1d.weight, self.carry if keep else None, self.carry_next if keep else None, ws.w, Bs, N, L, S,
+                             n, ldt, model.enc_nonlinear == "relu")
+        cln(ws.w, ws.wn, sep.norm1d, None, 0)
+        K.pw_gemm(B=1, M=Bn, K=N, T=T, ldt=ldt, A=sep.bottleneck_conv1d.weight, X=ws.wn, Y=ws.xa, bias=sep.bottleneck_conv1d.bias, a_amax=amax)
+        x, x_next = ws.xa, ws.xb
+        rings = self.rings.view(-1)
+        for li, layer in enumerate(self.layers):
+            dw = layer.separable_conv1d
+            d, P = layer.dilation, layer.kernel_size
+            K.pw_gemm(B=1, M=H, K=Bn, T=T, ldt=ldt, A=layer.bottleneck_conv1d.weight, X=x, Y=ws.ha, bias=layer.bottleneck_conv1d.bias, a_amax=amax)
+            cln(ws.ha, ws.hb, layer.norm1d, layer.nonlinear1d.weight, 1 + 2 * li)
+            K.online_depthwise_fwd(ws.hb, dw.depthwise_conv1d.weight, dw.depthwise_conv1d.bias, rings[self.ring_offsets[li]:], self.ring_len, ws.ha,
+                                   Bs, H, n, ldt, P, d)
+            cln(ws.ha, ws.hb, dw.norm1d, dw.nonlinear1d.weight, 2 + 2 * li)
+            out = dw.output_pointwise_conv1d if dw.dual_head else None
+            self._heads(K, ws.hb, out, dw.skip_pointwise_conv1d, x, x_next, ws.total, li == 0, T, ldt, amax)
+            if out is not None:
+                x, x_next = x_next, x
+        M = n_src * N
+        K.pw_gemm(B=1, M=M, K=Sc, T=T, ldt=ldt, A=sep.mask_conv1d.weight, X=ws.total, Y=ws.m, bias=sep.mask_conv1d.bias, pro_mode=PRO_PRELU,
+                  pro_alpha=sep.prelu.weight, epi_flags=EPI_SIGMOID if model.mask_nonlinear == "sigmoid" else 0, a_amax=amax)
+        if model.mask_nonlinear != "sigmoid":
+            K.softmax_ch_fwd(ws.m, 1, M, T, ldt)
+        K.online_decoder_fwd(ws.w, ws.m, model.decoder.conv_transpose1d.weight, self.tail if keep else None, self.tail_next if keep else None, ws.out,
+                             Bs, n_src, N, L, S, n, ldt)
+        K.online_advance(self.frames, self.carry if keep else None, self.carry_next if keep else None, keep, self.tail if keep else None,
+                         self.tail_next if keep else None, n_src * keep, Bs, n)
+
+    @staticmethod
+    def _heads(K, v, out, skip, x_res, x_out, total, first, T, ldt, amax):
+        """the two 1x1 heads of a layer as sepkernels.functional.PaddedHeadsFn.forward issues them: x_out = Wo v + bo + x_res, total (+)= Ws v + bs"""
+        H = v.shape[0]
+        Ws, bs = skip.weight, skip.bias
+        Sc = Ws.shape[0]
+        Wo, bo = (out.weight, out.bias) if out is not None else (None, None)
+        Bn = Wo.shape[0] if Wo is not None else 0
+        joint = Wo is not None and bo is not None and bs is not None and Bn % 128 == 0 and _net._adjacent(Wo, Ws) and _net._adjacent(bo, bs)
+        if joint:
+            K.pw_gemm(B=1, M=Bn + Sc, K=H, T=T, ldt=ldt, A=Wo.as_strided((Bn + Sc, H), (H, 1)), X=v, Y=x_out, Y2=total, m_split=Bn,
+                      bias=bo.as_strided((Bn + Sc,), (1,)), accumulate=int(not first), epi_flags=EPI_RESIDUAL, epi_res=x_res, a_amax=amax)
+            return
+        if Wo is not None:
+            K.pw_gemm(B=1, M=Bn, K=H, T=T, ldt=ldt, A=Wo, X=v, Y=x_out, bias=bo, epi_flags=EPI_RESIDUAL, epi_res=x_res, a_amax=amax)
+        K.pw_gemm(B=1, M=Sc, K=H, T=T, ldt=ldt, A=Ws, X=v, Y=total, bias=bs, accumulate=int(not first), a_amax=amax)
+
+    def launches_per_chunk(self):
+        """launches of one recorded chunk step (None before the first recorded chunk)"""
+        return len(self._seq) if self._seq is not None else None

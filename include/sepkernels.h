@@ -556,6 +556,39 @@ int sep_pit_finish(const float* best_val, const int64_t* best_idx, const int32_t
  *                   sep_pit_finish only forms loss[0] = sign * mean_b best_val[b] (the batch mean of SinkPIT's per-item losses, pit.py:155-156). */
 int sep_axpby(const float* x, float a, const float* y, float b, float* out, int64_t n, sep_stream_t stream);
 
+/* ---- online (chunk-by-chunk) separation of a causal Conv-TasNet (ABI 23, additive) ------------------------------------------------
+ * Symbols added to ABI 23 without changing any existing one.  sepkernels/online.py (OnlineSeparator) runs a chunk of n encoder frames of
+ * every stream (n S samples each) as one pass over STREAM-MAJOR columns: column j = stream * n + frame of a (C, ldt) matrix, ldt a multiple
+ * of 128 >= num_streams * n, columns beyond zero.  Per-stream state, all in device memory (a recorded chunk step replays correctly):
+ *   carry  (num_streams, L - S)           the last L - S input samples (starts as zeros: the pre-roll)
+ *   frames (num_streams) int64            encoder frames seen so far
+ *   sums   (num_streams, sums_stride)     fp64 {sum x, sum x^2} of every cLN, 2 per norm
+ *   ring   (num_streams, ring_stride)     per TCN layer the last (P - 1) d frames of its depthwise input, (C, (P - 1) d) in time order
+ *   tail   (num_streams, n_src, L - S)    overlap-add samples not yet final
+ * The reference formulas: filterbank.py:205-251 (encoder / decoder), modules/norm.py:58-101 (cLN), tdcn.py:125-132 (causal taps).
+ *   sep_online_encoder_fwd    w[nb][s n + f] = [ReLU] sum_k E[nb][k] ext_s[f S + k], ext_s = [carry_s | chunk_s]; carry_next_s = the last L - S
+ *                             samples of ext_s.  chunk (num_streams, n S).  carry / carry_next may be NULL when L == S.
+ *   sep_online_cln_fwd        y = (u - m_t) r_t gamma + beta with u = x or PReLU(x; alpha) (alpha may be NULL), m_t / r_t of norm.py:58-101 over
+ *                             everything the stream has seen: count C (t + 1), t = frames[s] + f.  sums (fp64) are read and updated.
+ *   sep_online_depthwise_fwd  y[c][s n + f] = bias[c] + sum_k w[c][k] ext[f + k d], ext = [ring (P - 1) d | x]; the ring takes the last (P - 1) d
+ *                             frames of ext.  Any P >= 2, (P - 1) d <= 16384.  bias may be NULL.
+ *   sep_online_decoder_fwd    out[s][src][i] (i < n S) and tail_next[s][src][i - n S] = tail[s][src][i] (i < L - S) + sum over the frames f of the
+ *                             chunk with f S <= i < f S + L of sum_nb w[nb][s n + f] mask[src N + nb][s n + f] D[nb][i - f S].
+ *   sep_online_advance        frames += n; carry <- carry_next; tail <- tail_next (carry_len, tail_len: floats per stream).  The last launch of a chunk.
+ *   sep_online_reset          for every stream s with mask[s] != 0: frames[s] = 0 and its slices of carry, sums, rings, tail (lengths per stream) = 0. */
+int sep_online_encoder_fwd(const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N, int L, int S,
+                           int n, int ldt, int relu, sep_stream_t stream);
+int sep_online_cln_fwd(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums, int sums_stride,
+                       const int64_t* frames, int num_streams, int C, int n, int ldt, float eps, sep_stream_t stream);
+int sep_online_depthwise_fwd(const float* x, const float* w, const float* bias, float* ring, int64_t ring_stride, float* y, int num_streams, int C,
+                             int n, int ldt, int P, int dilation, sep_stream_t stream);
+int sep_online_decoder_fwd(const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out, int num_streams,
+                           int n_src, int N, int L, int S, int n, int ldt, sep_stream_t stream);
+int sep_online_advance(int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next, int tail_len,
+                       int num_streams, int n, sep_stream_t stream);
+int sep_online_reset(const uint8_t* mask, int num_streams, int64_t* frames, float* carry, int carry_len, double* sums, int sums_len, float* rings,
+                     int64_t rings_len, float* tail, int tail_len, sep_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
