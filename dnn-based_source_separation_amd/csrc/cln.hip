@@ -281,7 +281,8 @@ __device__ __forceinline__ void chain_lookback(const unsigned long long* agg, co
 }
 
 // R = ceil(C / 64) rounds of 64 channels.  Thread (wave w, lane): channel 64 j + 8 w + (lane >> 3) in round j, frames 4 (lane & 7) .. + 3 of the tile.
-template <int R>
+// APPLY = false: the statistics alone (sep_cln_stats) -- the same sums in the same order, nothing of y is touched.
+template <int R, bool APPLY>
 __global__ __launch_bounds__(512) void cln_chain_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             const float* __restrict__ alpha, float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd,
                                                             int* __restrict__ ticket, unsigned long long* __restrict__ agg, unsigned long long* __restrict__ incl,
@@ -363,6 +364,7 @@ __global__ __launch_bounds__(512) void cln_chain_fwd_kernel(const float* __restr
             mr[1][f] = rf;                                                       // 0 for dead frames: they come out as zeros
         }
     }
+    if (!APPLY) return;
     __syncthreads();
     if (!inrow) return;
     const float4 m4 = ld4(&mr[0][4 * fl]), r4 = ld4(&mr[1][4 * fl]);
@@ -591,7 +593,7 @@ extern "C" int sep_cln_fwd(const float* x, const float* gamma, const float* beta
         SEP_REQUIRE((long)B * nt <= 0x7fffffffL / 4, "sep_cln_fwd: too many tiles");
         const ChainWs cw = chain_ws(ws, B, C, nt);
         SEP_REQUIRE(hipMemsetAsync(ws, 0, cw.clear_bytes, stream) == hipSuccess, "sep_cln: clearing the chain records failed");
-#define SEP_CLF(RR) hipLaunchKernelGGL((cln_chain_fwd_kernel<RR>), dim3(B * nt), dim3(512), 0, stream, x, gamma, beta, alpha, y, mean, rstd, cw.ticket, cw.agg, cw.incl, B, C, T, ldt, nt, eps)
+#define SEP_CLF(RR) hipLaunchKernelGGL((cln_chain_fwd_kernel<RR, true>), dim3(B * nt), dim3(512), 0, stream, x, gamma, beta, alpha, y, mean, rstd, cw.ticket, cw.agg, cw.incl, B, C, T, ldt, nt, eps)
         if (C <= 64) SEP_CLF(1); else if (C <= 128) SEP_CLF(2); else if (C <= 256) SEP_CLF(4); else SEP_CLF(8);
 #undef SEP_CLF
         SEP_CHECK_LAUNCH("sep_cln_fwd");
@@ -601,6 +603,30 @@ extern "C" int sep_cln_fwd(const float* x, const float* gamma, const float* beta
     hipLaunchKernelGGL(cln_scan_fwd_kernel, dim3(B), dim3(1024), 0, stream, (const double*)ws, mean, rstd, C, T, ldt, eps);
     hipLaunchKernelGGL(cln_apply_fwd_kernel, dim3(ceil_div(C, 4), B), dim3(256), 0, stream, x, (const float*)mean, (const float*)rstd, gamma, beta, alpha, y, C, T, ldt);
     SEP_CHECK_LAUNCH("sep_cln_fwd");
+    return 0;
+}
+
+/* sep_cln_fwd without the apply pass and without y: mean / rstd (B, ldt) alone, bit for bit what sep_cln_fwd writes (the same kernels, the
+ * same order of additions).  For a norm whose only consumer forms the normalised values itself (csrc/causal.hip). */
+extern "C" int sep_cln_stats(const float* x, float* mean, float* rstd, double* ws, int B, int C, int T, int ldt, float eps, const float* alpha,
+                             sep_stream_t stream_) {
+    SEP_REQUIRE(x && mean && rstd && ws && B > 0 && B <= 65535 && C > 0 && T > 0 && ldt >= T && ldt % 4 == 0, "sep_cln_stats: bad arguments");
+    hipStream_t stream = (hipStream_t)stream_;
+    static const bool three = getenv("SEPK_CLN_CHAIN") != nullptr && atoi(getenv("SEPK_CLN_CHAIN")) == 0;
+    if (chain_takes(C) && !three) {
+        const int nt = ceil_div(ldt, CH_TW);
+        SEP_REQUIRE((long)B * nt <= 0x7fffffffL / 4, "sep_cln_stats: too many tiles");
+        const ChainWs cw = chain_ws(ws, B, C, nt);
+        SEP_REQUIRE(hipMemsetAsync(ws, 0, cw.clear_bytes, stream) == hipSuccess, "sep_cln: clearing the chain records failed");
+#define SEP_CLS(RR) hipLaunchKernelGGL((cln_chain_fwd_kernel<RR, false>), dim3(B * nt), dim3(512), 0, stream, x, (const float*)nullptr, (const float*)nullptr, alpha, (float*)nullptr, mean, rstd, cw.ticket, cw.agg, cw.incl, B, C, T, ldt, nt, eps)
+        if (C <= 64) SEP_CLS(1); else if (C <= 128) SEP_CLS(2); else if (C <= 256) SEP_CLS(4); else SEP_CLS(8);
+#undef SEP_CLS
+        SEP_CHECK_LAUNCH("sep_cln_stats");
+        return 0;
+    }
+    hipLaunchKernelGGL((cln_colsums_kernel<false>), dim3(ceil_div(T, CLN_TCOLS), B), dim3(256), 0, stream, x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, alpha, ws, C, T, ldt);
+    hipLaunchKernelGGL(cln_scan_fwd_kernel, dim3(B), dim3(1024), 0, stream, (const double*)ws, mean, rstd, C, T, ldt, eps);
+    SEP_CHECK_LAUNCH("sep_cln_stats");
     return 0;
 }
 

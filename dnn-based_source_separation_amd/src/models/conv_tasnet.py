@@ -413,9 +413,9 @@ class ConvTasNet(nn.Module):
             encoder (+ReLU)                  EncodeFn                         sep_encoder_fwd
             cLN, 1x1 bottleneck              PaddedCLNFn, PaddedPointwiseFn   sep_cln_*, sep_pw_gemm
             per layer  1x1 -> PReLU+cLN -> depthwise (left padding (P-1) d) -> PReLU+cLN -> [1x1 output + residual ; 1x1 skip, summed]
-                                             PaddedPointwiseFn, PaddedCLNFn, PaddedDepthwiseFn, PaddedHeadsFn
-            PReLU + 1x1 mask, sigmoid | softmax, mask * w -> decoder -> crop     PaddedPointwiseFn, torch elementwise, MaskDecodeFn"""
-        from sepkernels.functional import EncodeFn, PaddedPointwiseFn, PaddedCLNFn, PaddedDepthwiseFn, PaddedHeadsFn, MaskDecodeFn
+                                             PaddedPointwiseFn, PaddedCLNDepthwiseFn, PaddedCLNFn, PaddedHeadsFn
+            PReLU + 1x1 mask, sigmoid | softmax, mask * w -> decoder -> crop     TailFn (net.tail_forward / tail_backward)"""
+        from sepkernels.functional import EncodeFn, PaddedPointwiseFn, PaddedCLNFn, PaddedCLNDepthwiseFn, PaddedHeadsFn, TailFn
         B, Cin, T = mixture.shape
         sep = self.separator
         geo = _net.Geometry(T, self.kernel_size, self.stride)
@@ -430,15 +430,23 @@ class ConvTasNet(nn.Module):
                 dw = layer.separable_conv1d
                 d, P = layer.dilation, layer.kernel_size
                 a = PaddedPointwiseFn.apply(x, F_, layer.bottleneck_conv1d.weight, layer.bottleneck_conv1d.bias, None, wa)
-                v1 = PaddedCLNFn.apply(a, F_, layer.nonlinear1d.weight, layer.norm1d.gamma, layer.norm1d.beta, layer.norm1d.eps)
-                z = PaddedDepthwiseFn.apply(v1, F_, dw.depthwise_conv1d.weight, dw.depthwise_conv1d.bias, d, (P - 1) * d)
+                # first norm + depthwise taps as one node: with the folded kernels (sep_cln_stats, sep_depthwise_cln_*) the normalised tensor
+                # is formed on load and never written; otherwise the sep_cln_fwd / sep_depthwise_fwd pair (sepkernels.functional.cln_depthwise_forward)
+                z = PaddedCLNDepthwiseFn.apply(a, F_, layer.nonlinear1d.weight, layer.norm1d.gamma, layer.norm1d.beta, layer.norm1d.eps,
+                                               dw.depthwise_conv1d.weight, dw.depthwise_conv1d.bias, d, (P - 1) * d)
                 v2 = PaddedCLNFn.apply(z, F_, dw.nonlinear1d.weight, dw.norm1d.gamma, dw.norm1d.beta, dw.norm1d.eps)
                 out = dw.output_pointwise_conv1d if dw.dual_head else None
                 x, total = PaddedHeadsFn.apply(v2, F_, out.weight if out is not None else None, out.bias if out is not None else None,
                                                dw.skip_pointwise_conv1d.weight, dw.skip_pointwise_conv1d.bias, x, total, wa)
-        m = PaddedPointwiseFn.apply(total, F_, sep.mask_conv1d.weight, sep.mask_conv1d.bias, sep.prelu.weight, wa)
-        m = torch.sigmoid(m) if self.mask_nonlinear == "sigmoid" else torch.softmax(m, dim=1)
-        out = MaskDecodeFn.apply(w, m, self.decoder.conv_transpose1d.weight, self.stride, T, want_latent)
+        # the tail as the fused path and the explicit causal driver (sepkernels/causal.py) run it: net.tail_forward / tail_backward behind one
+        # node -- the mask nonlinearity is the product's sigmoid epilogue | sep_softmax_ch_*, so the eager step and the recorded one round alike
+        import sepkernels
+        prev = sepkernels.set_weights_amax(wa)
+        try:
+            out = TailFn.apply(w, total, self.get_config(), geo, tuple(mixture.shape), want_latent, sep.prelu.weight, sep.mask_conv1d.weight,
+                               sep.mask_conv1d.bias, self.decoder.conv_transpose1d.weight)
+        finally:
+            sepkernels.set_weights_amax(prev)
         if want_latent:
             est, latent = out
             return est, latent[..., :F_]

@@ -49,6 +49,11 @@ def set_weights_amax(t):
     return prev
 
 
+def weights_amax():
+    """the bound set_weights_amax() last set, or None"""
+    return _weights_amax
+
+
 def gemm_arith_name():
     return {v: k for k, v in _ARITH_NAMES.items()}[gemm_arith()]
 
@@ -198,6 +203,11 @@ SIGNATURES = {
     "sep_online_decoder_fwd": [_vp] * 6 + [_I] * 7 + [_vp],
     "sep_online_advance": [_vp] * 3 + [_I] + [_vp] * 2 + [_I] * 3 + [_vp],
     "sep_online_reset": [_vp, _I, _vp, _vp, _I, _vp, _I, _vp, _L, _vp, _I, _vp],
+    # the causal layer's first norm folded into its depthwise kernels (ABI 23, additive): csrc/causal.hip, sepkernels/causal.py
+    "sep_cln_stats": [_vp] * 4 + [_I] * 4 + [_F, _vp, _vp],
+    "sep_depthwise_cln_fwd": [_vp] * 9 + [_I] * 7 + [_vp],
+    "sep_depthwise_cln_bwd_weight": [_vp] * 8 + [_I] * 7 + [_vp],
+    "sep_sum_f64": [_vp, _L, _vp, _vp],
 }
 _RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
              "sep_gln_tokens_ws_bytes": ctypes.c_size_t}
@@ -558,6 +568,22 @@ class HipBackend:
         _check(load().sep_cln_bwd(_ptr(dy, _f32), _ptr(x, _f32), _ptr(gamma, _f32), _ptr(mean, _f32), _ptr(rstd, _f32), _ptr(dx, _f32),
                                   _ptr(dgamma_part, _f32), _ptr(dbeta_part, _f32), _ptr(ws, _f64), B, C, T, ldt, eps, _ptr(alpha, _f32),
                                   _ptr(dalpha_part, _f32), _stream()), "sep_cln_bwd")
+
+    def sum_f64(self, x, n, out):
+        _check(load().sep_sum_f64(_ptr(x, _f32), n, _ptr(out, _f32), _stream()), "sep_sum_f64")
+
+    def cln_stats(self, x, mean, rstd, ws, B, C, T, ldt, eps, alpha=None):
+        _check(load().sep_cln_stats(_ptr(x, _f32), _ptr(mean, _f32), _ptr(rstd, _f32), _ptr(ws, _f64), B, C, T, ldt, eps, _ptr(alpha, _f32),
+                                    _stream()), "sep_cln_stats")
+
+    def depthwise_cln_fwd(self, x, alpha, gamma, beta, mean, rstd, w, bias, y, B, C, T, ldt, Kw, pad, dil):
+        _check(load().sep_depthwise_cln_fwd(_ptr(x, _f32), _ptr(alpha, _f32), _ptr(gamma, _f32), _ptr(beta, _f32), _ptr(mean, _f32), _ptr(rstd, _f32),
+                                            _ptr(w, _f32), _ptr(bias, _f32), _ptr(y, _f32), B, C, T, ldt, Kw, pad, dil, _stream()), "sep_depthwise_cln_fwd")
+
+    def depthwise_cln_bwd_weight(self, dy, x, alpha, gamma, beta, mean, rstd, partial, B, C, T, ldt, Kw, pad, dil):
+        _check(load().sep_depthwise_cln_bwd_weight(_ptr(dy, _f32), _ptr(x, _f32), _ptr(alpha, _f32), _ptr(gamma, _f32), _ptr(beta, _f32), _ptr(mean, _f32),
+                                                   _ptr(rstd, _f32), _ptr(partial, _f32), B, C, T, ldt, Kw, pad, dil, _stream()),
+               "sep_depthwise_cln_bwd_weight")
 
     def attn_fwd(self, qkv, o, lse, N, L, H, D, scale, p_drop=0.0, seed=0):
         _check(load().sep_attn_fwd(_ptr(qkv, _f32), _ptr(o, _f32), _ptr(lse, _f32), N, L, H, D, scale, p_drop, seed, _stream()), "sep_attn_fwd")

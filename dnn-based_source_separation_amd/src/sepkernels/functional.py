@@ -7,8 +7,11 @@ DPTNet / GALRNet / SepFormer (models/dptnet.py, galrnet.py, sepformer.py) start 
 bottleneck or no bottleneck at all; a gated tanh unit between the mask convolution and the decoder), so the same kernels are
 also exposed one operation at a time: EncodeFn, PaddedPointwiseFn, MaskDecodeFn.
 """
+import os
+
 import torch
 
+import sepkernels
 from . import backend, LSTM_INTERLEAVED, STATS_SLOTS
 from . import net as _net
 
@@ -56,6 +59,7 @@ class TailFn(torch.autograd.Function):
         core = core.contiguous()
         est, latent, m = _net.tail_forward(cfg, P, geo, w, core, mixture_shape, want_latent)
         ctx.cfg, ctx.geo, ctx.mixture_shape = cfg, geo, mixture_shape
+        ctx.amax = sepkernels.weights_amax()          # the pass's operand bound (SEP_ARITH_F16X3), if the caller set one: backward's products take the same
         ctx.save_for_backward(w, core, m, *params)
         ctx.set_materialize_grads(False)
         if want_latent:
@@ -71,7 +75,12 @@ class TailFn(torch.autograd.Function):
         K = backend()
         G = {k: torch.empty_like(p) for k, p in P.items()}
         dalpha = torch.zeros(1, device=w.device, dtype=torch.float64)
-        dcore, dwm = _net.tail_backward(ctx.cfg, P, ctx.geo, w, core, m, ctx.mixture_shape, d_est, G, dalpha)
+        prev = sepkernels.set_weights_amax(ctx.amax) if ctx.amax is not None else None
+        try:
+            dcore, dwm = _net.tail_backward(ctx.cfg, P, ctx.geo, w, core, m, ctx.mixture_shape, d_est, G, dalpha)
+        finally:
+            if ctx.amax is not None:
+                sepkernels.set_weights_amax(prev)
         K.f64_to_f32(dalpha, G["separator.prelu.weight"], 1, 0)
         return (dwm, dcore, None, None, None, None) + tuple(G[k] for k in TAIL_KEYS)
 
@@ -112,6 +121,45 @@ class EncodeFn(torch.autograd.Function):
         return None, dE, None, None
 
 
+# ---- the staged (causal) layers' operations as plain functions on tensors: the autograd Functions below and the explicit driver of
+# sepkernels/causal.py (the recorded causal training step) both call these, so there is one statement of every launch.  The optional
+# destinations (dW, db, dgamma, ...) let the driver have the gradients written straight into its flat gradient buffer.
+def pointwise_forward(x, n_frames, weight, bias, alpha, a_amax=None):
+    K = backend()
+    B, Cin, ldt = x.shape
+    Cout = weight.shape[0]
+    if Cin % 16 or Cout % 16:
+        raise NotImplementedError("PaddedPointwiseFn: channel counts must be multiples of 16 (got {} -> {})".format(Cin, Cout))
+    y = torch.empty(B, Cout, ldt, device=x.device, dtype=x.dtype)
+    pro = dict(pro_mode=_net.PRO_PRELU, pro_alpha=alpha) if alpha is not None else {}
+    K.pw_gemm(B=B, M=Cout, K=Cin, T=n_frames, ldt=ldt, A=weight, X=x, Y=y, bias=bias, a_amax=a_amax, **pro)
+    return y
+
+
+def pointwise_backward(x, weight, alpha, a_amax, n_frames, has_bias, dy, dW=None, db=None):
+    """-> dx, dW, db (None without a bias), dalpha (None without a slope).  dW / db: where to write the parameter gradients."""
+    K = backend()
+    B, Cin, ldt = x.shape
+    Cout, F = weight.shape[0], n_frames
+    f32 = dict(device=x.device, dtype=x.dtype)
+    dx = torch.empty(B, Cin, ldt, **f32)
+    dalpha = None
+    if alpha is None:
+        K.pw_gemm(B=B, M=Cin, K=Cout, T=F, ldt=ldt, trans_a=1, A=weight, X=dy, Y=dx, a_amax=a_amax)
+        part, pb, ns = _net._wgrad(K, B, F, ldt, 0.0, f32, Cout, Cin, dy, x, True)
+    else:
+        slot = torch.zeros(1, device=x.device, dtype=torch.float64)
+        K.pw_gemm(B=B, M=Cin, K=Cout, T=F, ldt=ldt, trans_a=1, A=weight, X=dy, Y=dx, epi_flags=_net.EPI_PRELU_BWD, epi_aux=x,
+                  epi_alpha=alpha, epi_dalpha=slot, a_amax=a_amax)
+        part, pb, ns = _net._wgrad(K, B, F, ldt, 0.0, f32, Cout, Cin, dy, x, True, x_mode=_net.PRO_PRELU, x_alpha=alpha)
+        dalpha = torch.empty_like(alpha)
+        K.f64_to_f32(slot, dalpha, 1, 0)
+    dW = torch.empty_like(weight) if dW is None else dW
+    db = torch.empty(Cout, **f32) if db is None else db
+    K.reduce_slabs([(part, 0, dW, Cout * Cin, ns, Cout * Cin, 0, 1.0), (pb, 0, db, Cout, ns, Cout, 0, 1.0)])
+    return dx, dW, (db if has_bias else None), dalpha
+
+
 class PaddedPointwiseFn(torch.autograd.Function):
     """[PReLU ->] nn.Conv1d(kernel_size=1) on rows that already carry the workspace stride: x (B, Cin, ldt) with n_frames
     valid frames -> (B, Cout, ldt), frames beyond zero.  `alpha` (the single PReLU slope) or None.  Same kernels as
@@ -122,41 +170,18 @@ class PaddedPointwiseFn(torch.autograd.Function):
     def forward(ctx, x, n_frames, weight, bias, alpha, a_amax=None):
         """a_amax: (1,) device tensor >= max|w| over the weights of this and the backward product (SEP_ARITH_F16X3's operand bound), or None:
         the binding then forms it per call (two small reductions); a model that makes dozens of these calls per pass hands over ONE bound"""
-        K = backend()
         x = x.contiguous()
-        B, Cin, ldt = x.shape
-        Cout = weight.shape[0]
-        if Cin % 16 or Cout % 16:
-            raise NotImplementedError("PaddedPointwiseFn: channel counts must be multiples of 16 (got {} -> {})".format(Cin, Cout))
-        y = torch.empty(B, Cout, ldt, device=x.device, dtype=x.dtype)
-        pro = dict(pro_mode=_net.PRO_PRELU, pro_alpha=alpha) if alpha is not None else {}
-        K.pw_gemm(B=B, M=Cout, K=Cin, T=n_frames, ldt=ldt, A=weight, X=x, Y=y, bias=bias, a_amax=a_amax, **pro)
+        y = pointwise_forward(x, n_frames, weight, bias, alpha, a_amax)
         ctx.save_for_backward(x, weight, alpha, a_amax)
-        ctx.meta = (B, Cin, Cout, n_frames, ldt, bias is not None)
+        ctx.meta = (n_frames, bias is not None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        K = backend()
         x, weight, alpha, a_amax = ctx.saved_tensors
-        B, Cin, Cout, F, ldt, has_bias = ctx.meta
-        f32 = dict(device=x.device, dtype=x.dtype)
-        dy = dy.contiguous()
-        dx = torch.empty(B, Cin, ldt, **f32)
-        dalpha = None
-        if alpha is None:
-            K.pw_gemm(B=B, M=Cin, K=Cout, T=F, ldt=ldt, trans_a=1, A=weight, X=dy, Y=dx, a_amax=a_amax)
-            part, pb, ns = _net._wgrad(K, B, F, ldt, 0.0, f32, Cout, Cin, dy, x, True)
-        else:
-            slot = torch.zeros(1, device=x.device, dtype=torch.float64)
-            K.pw_gemm(B=B, M=Cin, K=Cout, T=F, ldt=ldt, trans_a=1, A=weight, X=dy, Y=dx, epi_flags=_net.EPI_PRELU_BWD, epi_aux=x,
-                      epi_alpha=alpha, epi_dalpha=slot, a_amax=a_amax)
-            part, pb, ns = _net._wgrad(K, B, F, ldt, 0.0, f32, Cout, Cin, dy, x, True, x_mode=_net.PRO_PRELU, x_alpha=alpha)
-            dalpha = torch.empty_like(alpha)
-            K.f64_to_f32(slot, dalpha, 1, 0)
-        dW, db = torch.empty_like(weight), torch.empty(Cout, **f32)
-        K.reduce_slabs([(part, 0, dW, Cout * Cin, ns, Cout * Cin, 0, 1.0), (pb, 0, db, Cout, ns, Cout, 0, 1.0)])
-        return dx, None, dW, (db if has_bias else None), dalpha, None
+        F, has_bias = ctx.meta
+        dx, dW, db, dalpha = pointwise_backward(x, weight, alpha, a_amax, F, has_bias, dy.contiguous())
+        return dx, None, dW, db, dalpha, None
 
 
 class MaskDecodeFn(torch.autograd.Function):
@@ -209,6 +234,50 @@ def cln_workspace(K, B, C, T, ldt, device):
     return torch.empty((K.cln_ws_bytes(B, C, T, ldt) + 7) // 8, device=device, dtype=torch.float64)
 
 
+def cln_forward(x, n_frames, alpha, g1, b1, eps, stats_only=False):
+    """-> y, mean, rstd.  stats_only: the statistics alone (sep_cln_stats; y is None) for a norm whose consumer forms the values itself"""
+    K = backend()
+    B, C, ldt = x.shape
+    f32 = dict(device=x.device, dtype=x.dtype)
+    mean, rstd = torch.empty(B, ldt, **f32), torch.empty(B, ldt, **f32)
+    ws = cln_workspace(K, B, C, n_frames, ldt, x.device)
+    if stats_only:
+        K.cln_stats(x, mean, rstd, ws, B, C, n_frames, ldt, eps, alpha=alpha)
+        return None, mean, rstd
+    y = torch.empty(B, C, ldt, **f32)
+    K.cln_fwd(x, g1, b1, y, mean, rstd, ws, B, C, n_frames, ldt, eps, alpha=alpha)
+    return y, mean, rstd
+
+
+def cln_backward(dy, x, g1, mean, rstd, alpha, n_frames, eps, dgamma=None, dbeta=None, dalpha=None):
+    """-> dx, dgamma (C), dbeta (C), dalpha.  With destinations given (the explicit driver) the slope's B * C row partials are summed by the
+    library too (sep_sum_f64: accumulated in fp64, as torch's sum) into dalpha (1,); without, as before, by torch in fp64."""
+    K = backend()
+    B, C, ldt = x.shape
+    F = n_frames
+    f32 = dict(device=x.device, dtype=x.dtype)
+    dx = torch.empty(B, C, ldt, **f32)
+    pg, pb = torch.empty(B, C, **f32), torch.empty(B, C, **f32)
+    pa = torch.empty(B, C, **f32) if alpha is not None else None
+    ws = cln_workspace(K, B, C, F, ldt, x.device)
+    K.cln_bwd(dy, x, g1, mean, rstd, dx, pg, pb, ws, B, C, F, ldt, eps, alpha=alpha, dalpha_part=pa)
+    dgamma = torch.empty(C, **f32) if dgamma is None else dgamma
+    dbeta = torch.empty(C, **f32) if dbeta is None else dbeta
+    segs = [(pg, 0, dgamma, C, B, C, 0, 1.0), (pb, 0, dbeta, C, B, C, 0, 1.0)]
+    if alpha is not None and dalpha is not None:
+        if hasattr(K, "sum_f64"):
+            K.reduce_slabs(segs)
+            K.sum_f64(pa, B * C, dalpha)
+        else:                                    # (the CPU emulator of the tests: two sep_reduce_slabs stages, over the samples, then over the channels)
+            pac = torch.empty(C, **f32)
+            K.reduce_slabs(segs + [(pa, 0, pac, C, B, C, 0, 1.0)])
+            K.reduce_slabs([(pac, 0, dalpha, 1, C, 1, 0, 1.0)])
+        return dx, dgamma, dbeta, dalpha
+    K.reduce_slabs(segs)
+    dalpha = pa.sum(dtype=torch.float64).to(x.dtype).view(alpha.shape) if alpha is not None else None      # B*C row partials -> the one slope
+    return dx, dgamma, dbeta, dalpha
+
+
 class PaddedCLNFn(torch.autograd.Function):
     """[PReLU ->] CumulativeLayerNorm1d on rows that already carry the workspace stride: x (B, C, ldt) with n_frames valid frames -> the
     same shape, frames beyond zero (reference src/modules/norm.py:58-101, behind nonlinear1d of tdcn.py:113-116 / 182-186 when `alpha` -- the
@@ -217,35 +286,77 @@ class PaddedCLNFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n_frames, alpha, gamma, beta, eps):
-        K = backend()
         x = x.contiguous()
-        B, C, ldt = x.shape
-        f32 = dict(device=x.device, dtype=x.dtype)
         g1, b1 = gamma.reshape(-1).contiguous(), beta.reshape(-1).contiguous()
-        y = torch.empty(B, C, ldt, **f32)
-        mean, rstd = torch.empty(B, ldt, **f32), torch.empty(B, ldt, **f32)
-        ws = cln_workspace(K, B, C, n_frames, ldt, x.device)
-        K.cln_fwd(x, g1, b1, y, mean, rstd, ws, B, C, n_frames, ldt, eps, alpha=alpha)
+        y, mean, rstd = cln_forward(x, n_frames, alpha, g1, b1, eps)
         ctx.save_for_backward(x, g1, mean, rstd, alpha)
-        ctx.meta = (B, C, n_frames, ldt, eps, gamma.shape, beta.shape)
+        ctx.meta = (n_frames, eps, gamma.shape, beta.shape)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        K = backend()
         x, g1, mean, rstd, alpha = ctx.saved_tensors
-        B, C, F, ldt, eps, gshape, bshape = ctx.meta
-        f32 = dict(device=x.device, dtype=x.dtype)
-        dx = torch.empty(B, C, ldt, **f32)
-        pg, pb = torch.empty(B, C, **f32), torch.empty(B, C, **f32)
-        pa = torch.empty(B, C, **f32) if alpha is not None else None
-        ws = cln_workspace(K, B, C, F, ldt, x.device)
-        K.cln_bwd(dy.contiguous(), x, g1, mean, rstd, dx, pg, pb, ws, B, C, F, ldt, eps, alpha=alpha, dalpha_part=pa)
-        dgamma, dbeta = torch.empty(C, **f32), torch.empty(C, **f32)
-        segs = [(pg, 0, dgamma, C, B, C, 0, 1.0), (pb, 0, dbeta, C, B, C, 0, 1.0)]
-        K.reduce_slabs(segs)
-        dalpha = pa.sum(dtype=torch.float64).to(x.dtype).view(alpha.shape) if alpha is not None else None      # B*C row partials -> the one slope
+        F, eps, gshape, bshape = ctx.meta
+        dx, dgamma, dbeta, dalpha = cln_backward(dy.contiguous(), x, g1, mean, rstd, alpha, F, eps)
         return dx, None, dalpha, dgamma.view(gshape), dbeta.view(bshape), None
+
+
+def heads_forward(v, n_frames, Wo, bo, Ws, bs, x_res, total, a_amax=None):
+    """-> xo (None without the output head), total (created when None, else updated in place)"""
+    K = backend()
+    B, H, ldt = v.shape
+    Sc = Ws.shape[0]
+    Bn = Wo.shape[0] if Wo is not None else 0
+    f32 = dict(device=v.device, dtype=v.dtype)
+    first = total is None
+    if first:
+        total = torch.empty(B, Sc, ldt, **f32)
+    xo = torch.empty(B, Bn, ldt, **f32) if Wo is not None else None
+    joint = Wo is not None and bo is not None and bs is not None and Bn % 128 == 0 and _net._adjacent(Wo, Ws) and _net._adjacent(bo, bs)
+    if joint:
+        K.pw_gemm(B=B, M=Bn + Sc, K=H, T=n_frames, ldt=ldt, A=Wo.as_strided((Bn + Sc, H), (H, 1)), X=v, Y=xo, Y2=total, m_split=Bn,
+                  bias=bo.as_strided((Bn + Sc,), (1,)), accumulate=int(not first), epi_flags=_net.EPI_RESIDUAL, epi_res=x_res, a_amax=a_amax)
+    else:
+        if Wo is not None:
+            K.pw_gemm(B=B, M=Bn, K=H, T=n_frames, ldt=ldt, A=Wo, X=v, Y=xo, bias=bo, epi_flags=_net.EPI_RESIDUAL, epi_res=x_res, a_amax=a_amax)
+        K.pw_gemm(B=B, M=Sc, K=H, T=n_frames, ldt=ldt, A=Ws, X=v, Y=total, bias=bs, accumulate=int(not first), a_amax=a_amax)
+    return xo, total
+
+
+def heads_backward(v, Wo, Ws, a_amax, n_frames, d_out, d_total, dWo=None, dbo=None, dWs=None, dbs=None):
+    """-> dv, dWo, dbo (None without the output head or its gradient), dWs, dbs.  d_total must be given (B, Sc, ldt)."""
+    K = backend()
+    B, H, ldt = v.shape
+    F = n_frames
+    Sc = Ws.shape[0]
+    Bn = Wo.shape[0] if Wo is not None else 0
+    f32 = dict(device=v.device, dtype=v.dtype)
+    have_o = Wo is not None and d_out is not None
+    dv = torch.empty(B, H, ldt, **f32)
+    if have_o:
+        K.pw_gemm(B=B, M=H, K=Bn + Sc, T=F, ldt=ldt, trans_a=1, A=Wo, A2=Ws, X=d_out, X2=d_total, k_split=Bn, Y=dv, a_amax=a_amax)
+    else:
+        K.pw_gemm(B=B, M=H, K=Sc, T=F, ldt=ldt, trans_a=1, A=Ws, X=d_total, Y=dv, a_amax=a_amax)
+    segs = []
+    dWs = torch.empty_like(Ws) if dWs is None else dWs
+    dbs = torch.empty(Sc, **f32) if dbs is None else dbs
+    if have_o:
+        dWo = torch.empty_like(Wo) if dWo is None else dWo
+        dbo = torch.empty(Bn, **f32) if dbo is None else dbo
+    else:
+        dWo = dbo = None
+    if have_o and Bn % 128 == 0:
+        part, pb, ns = _net._wgrad(K, B, F, ldt, 0.0, f32, Bn + Sc, H, d_out, v, True, G2=d_total, g_split=Bn)
+        segs += [(part, 0, dWo, Bn * H, ns, (Bn + Sc) * H, 0, 1.0), (part, Bn * H, dWs, Sc * H, ns, (Bn + Sc) * H, 0, 1.0),
+                 (pb, 0, dbo, Bn, ns, Bn + Sc, 0, 1.0), (pb, Bn, dbs, Sc, ns, Bn + Sc, 0, 1.0)]
+    else:
+        if have_o:
+            part, pb, ns = _net._wgrad(K, B, F, ldt, 0.0, f32, Bn, H, d_out, v, True)
+            segs += [(part, 0, dWo, Bn * H, ns, Bn * H, 0, 1.0), (pb, 0, dbo, Bn, ns, Bn, 0, 1.0)]
+        part2, pb2, ns2 = _net._wgrad(K, B, F, ldt, 0.0, f32, Sc, H, d_total, v, True)
+        segs += [(part2, 0, dWs, Sc * H, ns2, Sc * H, 0, 1.0), (pb2, 0, dbs, Sc, ns2, Sc, 0, 1.0)]
+    K.reduce_slabs(segs)
+    return dv, dWo, dbo, dWs, dbs
 
 
 class PaddedHeadsFn(torch.autograd.Function):
@@ -258,65 +369,67 @@ class PaddedHeadsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, v, n_frames, Wo, bo, Ws, bs, x_res, total, a_amax=None):
-        K = backend()
         v = v.contiguous()
-        B, H, ldt = v.shape
-        Sc = Ws.shape[0]
-        Bn = Wo.shape[0] if Wo is not None else 0
-        f32 = dict(device=v.device, dtype=v.dtype)
         first = total is None
-        if first:
-            total = torch.empty(B, Sc, ldt, **f32)
-        else:
+        if not first:
             ctx.mark_dirty(total)
-        xo = torch.empty(B, Bn, ldt, **f32) if Wo is not None else None
-        joint = Wo is not None and bo is not None and bs is not None and Bn % 128 == 0 and _net._adjacent(Wo, Ws) and _net._adjacent(bo, bs)
-        if joint:
-            K.pw_gemm(B=B, M=Bn + Sc, K=H, T=n_frames, ldt=ldt, A=Wo.as_strided((Bn + Sc, H), (H, 1)), X=v, Y=xo, Y2=total, m_split=Bn,
-                      bias=bo.as_strided((Bn + Sc,), (1,)), accumulate=int(not first), epi_flags=_net.EPI_RESIDUAL, epi_res=x_res, a_amax=a_amax)
-        else:
-            if Wo is not None:
-                K.pw_gemm(B=B, M=Bn, K=H, T=n_frames, ldt=ldt, A=Wo, X=v, Y=xo, bias=bo, epi_flags=_net.EPI_RESIDUAL, epi_res=x_res, a_amax=a_amax)
-            K.pw_gemm(B=B, M=Sc, K=H, T=n_frames, ldt=ldt, A=Ws, X=v, Y=total, bias=bs, accumulate=int(not first), a_amax=a_amax)
+        xo, total = heads_forward(v, n_frames, Wo, bo, Ws, bs, x_res, total, a_amax)
         ctx.save_for_backward(v, Wo, Ws, a_amax)
-        ctx.meta = (B, H, Bn, Sc, n_frames, ldt, first)
+        ctx.meta = (n_frames, first)
         ctx.set_materialize_grads(False)
         return (xo, total) if Wo is not None else (None, total)
 
     @staticmethod
     def backward(ctx, d_out, d_total):
-        K = backend()
         v, Wo, Ws, a_amax = ctx.saved_tensors
-        B, H, Bn, Sc, F, ldt, first = ctx.meta
-        f32 = dict(device=v.device, dtype=v.dtype)
+        F, first = ctx.meta
         if d_total is None:
-            d_total = torch.zeros(B, Sc, ldt, **f32)
+            d_total = torch.zeros(v.shape[0], Ws.shape[0], v.shape[2], device=v.device, dtype=v.dtype)
         d_total = d_total.contiguous()
         have_o = Wo is not None and d_out is not None
         if have_o:
             d_out = d_out.contiguous()
-        dv = torch.empty(B, H, ldt, **f32)
-        if have_o:
-            K.pw_gemm(B=B, M=H, K=Bn + Sc, T=F, ldt=ldt, trans_a=1, A=Wo, A2=Ws, X=d_out, X2=d_total, k_split=Bn, Y=dv, a_amax=a_amax)
-        else:
-            K.pw_gemm(B=B, M=H, K=Sc, T=F, ldt=ldt, trans_a=1, A=Ws, X=d_total, Y=dv, a_amax=a_amax)
-        segs = []
-        dWo = dbo = None
-        dWs, dbs = torch.empty_like(Ws), torch.empty(Sc, **f32)
-        if have_o and Bn % 128 == 0:
-            dWo, dbo = torch.empty_like(Wo), torch.empty(Bn, **f32)
-            part, pb, ns = _net._wgrad(K, B, F, ldt, 0.0, f32, Bn + Sc, H, d_out, v, True, G2=d_total, g_split=Bn)
-            segs += [(part, 0, dWo, Bn * H, ns, (Bn + Sc) * H, 0, 1.0), (part, Bn * H, dWs, Sc * H, ns, (Bn + Sc) * H, 0, 1.0),
-                     (pb, 0, dbo, Bn, ns, Bn + Sc, 0, 1.0), (pb, Bn, dbs, Sc, ns, Bn + Sc, 0, 1.0)]
-        else:
-            if have_o:
-                dWo, dbo = torch.empty_like(Wo), torch.empty(Bn, **f32)
-                part, pb, ns = _net._wgrad(K, B, F, ldt, 0.0, f32, Bn, H, d_out, v, True)
-                segs += [(part, 0, dWo, Bn * H, ns, Bn * H, 0, 1.0), (pb, 0, dbo, Bn, ns, Bn, 0, 1.0)]
-            part2, pb2, ns2 = _net._wgrad(K, B, F, ldt, 0.0, f32, Sc, H, d_total, v, True)
-            segs += [(part2, 0, dWs, Sc * H, ns2, Sc * H, 0, 1.0), (pb2, 0, dbs, Sc, ns2, Sc, 0, 1.0)]
-        K.reduce_slabs(segs)
+        dv, dWo, dbo, dWs, dbs = heads_backward(v, Wo, Ws, a_amax, F, d_out if have_o else None, d_total)
         return dv, None, dWo, dbo, dWs, dbs, (d_out if have_o else None), (None if first else d_total), None
+
+
+def depthwise_forward(x, weight, bias, dilation, left):
+    K = backend()
+    B, C, ldt = x.shape
+    Kw = weight.shape[-1]
+    y = torch.empty(B, C, ldt, device=x.device, dtype=x.dtype)
+    K.depthwise_fwd(x, weight, bias, y, B, C, ldt, ldt, Kw, 1, left, dilation)
+    return y
+
+
+def _depthwise_param_grads(K, part, B, C, Kw, f32, dweight, dbias, has_bias):
+    """(B, C, Kw + 1) per-sample partials -> d weight (C, 1, Kw), d bias (C).  With destinations given (the explicit driver) the split of the
+    summed (C, Kw + 1) rows into the two parameters is two sep_repack copies; without, as before, torch slices."""
+    if dweight is None:
+        dwb = torch.empty(C * (Kw + 1), **f32)
+        K.reduce_slabs([(part, 0, dwb, C * (Kw + 1), B, C * (Kw + 1), 0, 1.0)])
+        dwb = dwb.view(C, Kw + 1)
+        return dwb[:, :Kw].reshape(C, 1, Kw).contiguous(), (dwb[:, Kw].contiguous() if has_bias else None)
+    dwb = torch.empty((C + 1) * (Kw + 1), **f32)               # (one spare row: the bias column is read as rows of Kw + 1 starting at word Kw)
+    K.reduce_slabs([(part, 0, dwb[:C * (Kw + 1)], C * (Kw + 1), B, C * (Kw + 1), 0, 1.0)])
+    K.repack(dwb[:C * (Kw + 1)], Kw + 1, dweight, Kw, C, Kw)
+    if dbias is not None:
+        K.repack(dwb[Kw:Kw + C * (Kw + 1)], Kw + 1, dbias, 1, C, 1)
+    return dweight, dbias
+
+
+def depthwise_backward(dy, x, weight, dilation, left, has_bias, dweight=None, dbias=None):
+    """-> dx, d weight, d bias.  dy must be zero beyond the valid frames (it comes out of a kernel that writes the pad frames)."""
+    K = backend()
+    B, C, ldt = x.shape
+    Kw = weight.shape[-1]
+    f32 = dict(device=x.device, dtype=x.dtype)
+    dx = torch.empty(B, C, ldt, **f32)
+    K.depthwise_bwd_input(dy, weight, dx, B, C, ldt, ldt, Kw, 1, left, dilation)
+    part = torch.empty(B, C, Kw + 1, **f32)
+    K.depthwise_bwd_weight(dy, x, part, B, C, ldt, ldt, Kw, 1, left, dilation)
+    dW, db = _depthwise_param_grads(K, part, B, C, Kw, f32, dweight, dbias, has_bias)
+    return dx, dW, db
 
 
 class PaddedDepthwiseFn(torch.autograd.Function):
@@ -327,31 +440,83 @@ class PaddedDepthwiseFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n_frames, weight, bias, dilation, left):
-        K = backend()
         x = x.contiguous()
-        B, C, ldt = x.shape
-        Kw = weight.shape[-1]
-        y = torch.empty(B, C, ldt, device=x.device, dtype=x.dtype)
-        K.depthwise_fwd(x, weight, bias, y, B, C, ldt, ldt, Kw, 1, left, dilation)
+        y = depthwise_forward(x, weight, bias, dilation, left)
         ctx.save_for_backward(x, weight)
-        ctx.meta = (B, C, ldt, Kw, dilation, left, bias is not None)
+        ctx.meta = (dilation, left, bias is not None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        K = backend()
         x, weight = ctx.saved_tensors
-        B, C, ldt, Kw, dilation, left, has_bias = ctx.meta
-        dy = dy.contiguous()                                     # zero beyond n_frames: it comes out of a kernel that writes the pad frames
-        f32 = dict(device=x.device, dtype=x.dtype)
-        dx = torch.empty(B, C, ldt, **f32)
-        K.depthwise_bwd_input(dy, weight, dx, B, C, ldt, ldt, Kw, 1, left, dilation)
+        dilation, left, has_bias = ctx.meta
+        dx, dW, db = depthwise_backward(dy.contiguous(), x, weight, dilation, left, has_bias)
+        return dx, None, dW, db, None, None
+
+
+def causal_fold():
+    """True when the first norm of a causal TCN layer is folded into its depthwise kernels (sep_cln_stats + sep_depthwise_cln_*: the
+    normalised tensor never exists in memory): whenever the backend has those calls, unless SEPK_CAUSAL_FOLD=0 asks for the two-kernel form."""
+    return hasattr(backend(), "depthwise_cln_fwd") and os.environ.get("SEPK_CAUSAL_FOLD", "1") != "0"
+
+
+def cln_depthwise_forward(a, n_frames, alpha, g1, b1, eps, weight, bias, dilation, left):
+    """z = depthwise(pad(cLN(PReLU(a)))) of a causal TCN layer (reference tdcn.py:107-132) -> z, saved.  Folded: sep_cln_stats, then
+    sep_depthwise_cln_fwd forms the normalised values on load; else sep_cln_fwd writes them (v1) and sep_depthwise_fwd reads them."""
+    K = backend()
+    B, C, ldt = a.shape
+    Kw = weight.shape[-1]
+    if causal_fold():
+        _, mean, rstd = cln_forward(a, n_frames, alpha, g1, b1, eps, stats_only=True)
+        z = torch.empty(B, C, ldt, device=a.device, dtype=a.dtype)
+        K.depthwise_cln_fwd(a, alpha, g1, b1, mean, rstd, weight, bias, z, B, C, n_frames, ldt, Kw, left, dilation)
+        return z, (mean, rstd, None)
+    v1, mean, rstd = cln_forward(a, n_frames, alpha, g1, b1, eps)
+    return depthwise_forward(v1, weight, bias, dilation, left), (mean, rstd, v1)
+
+
+def cln_depthwise_backward(dz, a, saved, alpha, g1, b1, eps, n_frames, weight, dilation, left, has_bias, dweight=None, dbias=None, dgamma=None,
+                           dbeta=None, dalpha=None):
+    """-> da, d weight, d bias, dgamma, dbeta, dalpha: the depthwise backward (input gradient; weight gradient against v1, kept or re-formed
+    on load), then the norm's"""
+    K = backend()
+    mean, rstd, v1 = saved
+    B, C, ldt = a.shape
+    Kw = weight.shape[-1]
+    if v1 is not None:
+        dv1, dW, db = depthwise_backward(dz, v1, weight, dilation, left, has_bias, dweight, dbias)
+    else:
+        f32 = dict(device=a.device, dtype=a.dtype)
+        dv1 = torch.empty(B, C, ldt, **f32)
+        K.depthwise_bwd_input(dz, weight, dv1, B, C, ldt, ldt, Kw, 1, left, dilation)
         part = torch.empty(B, C, Kw + 1, **f32)
-        K.depthwise_bwd_weight(dy, x, part, B, C, ldt, ldt, Kw, 1, left, dilation)
-        dwb = torch.empty(C * (Kw + 1), **f32)
-        K.reduce_slabs([(part, 0, dwb, C * (Kw + 1), B, C * (Kw + 1), 0, 1.0)])
-        dwb = dwb.view(C, Kw + 1)
-        return dx, None, dwb[:, :Kw].reshape(C, 1, Kw).contiguous(), (dwb[:, Kw].contiguous() if has_bias else None), None, None
+        K.depthwise_cln_bwd_weight(dz, a, alpha, g1, b1, mean, rstd, part, B, C, n_frames, ldt, Kw, left, dilation)
+        dW, db = _depthwise_param_grads(K, part, B, C, Kw, f32, dweight, dbias, has_bias)
+    da, dgamma, dbeta, dalpha = cln_backward(dv1, a, g1, mean, rstd, alpha, n_frames, eps, dgamma, dbeta, dalpha)
+    return da, dW, db, dgamma, dbeta, dalpha
+
+
+class PaddedCLNDepthwiseFn(torch.autograd.Function):
+    """PaddedCLNFn followed by PaddedDepthwiseFn as ONE node: [PReLU ->] cLN -> zero padding -> depthwise taps of a causal TCN layer.  The same
+    launches as the pair where the backend has no folded kernels (and under SEPK_CAUSAL_FOLD=0); with them the normalised tensor is neither
+    written nor kept for backward (cln_depthwise_forward)."""
+
+    @staticmethod
+    def forward(ctx, a, n_frames, alpha, gamma, beta, eps, weight, bias, dilation, left):
+        a = a.contiguous()
+        g1, b1 = gamma.reshape(-1).contiguous(), beta.reshape(-1).contiguous()
+        z, (mean, rstd, v1) = cln_depthwise_forward(a, n_frames, alpha, g1, b1, eps, weight, bias, dilation, left)
+        ctx.save_for_backward(a, g1, b1, mean, rstd, v1, alpha, weight)
+        ctx.meta = (n_frames, eps, gamma.shape, beta.shape, dilation, left, bias is not None)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        a, g1, b1, mean, rstd, v1, alpha, weight = ctx.saved_tensors
+        F, eps, gshape, bshape, dilation, left, has_bias = ctx.meta
+        da, dW, db, dgamma, dbeta, dalpha = cln_depthwise_backward(dz.contiguous(), a, (mean, rstd, v1), alpha, g1, b1, eps, F, weight, dilation,
+                                                                   left, has_bias)
+        return da, None, dalpha, dgamma.view(gshape), dbeta.view(bshape), None, dW, db, None, None
 
 
 def segment_geometry(T, chunk_size, hop_size):

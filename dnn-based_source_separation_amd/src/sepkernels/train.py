@@ -20,6 +20,8 @@ ABI 23).  The two scalars that change from step to step (Adam's step count, the 
 (profiles/r07_round5_experiments.md, r07m) and that path (FusedTrainStep.capture, GraphedStep) is gone.  With ranks > 1 the gradient buckets
 cut the recorded list into segments: a replayed step runs a segment, issues that bucket's asynchronous all-reduce, runs the next segment ...,
 waits for the exchange, then runs clip + Adam (`_seq_marks`).
+The staged causal family (model.staged) records through its own explicit driver, sepkernels/causal.py, in place of net._forward / net._backward; the criterion, clip
+and Adam parts of the recording are the same code.  With a gradient exchange it steps eagerly (recordable() says so).
 """
 import os
 
@@ -33,8 +35,10 @@ class FusedTrainStep:
     def __init__(self, model, criterion, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=5.0,
                  process_group=None, distributed=None, uneven_batches=False, time_collectives=False, exercise_collectives=False, auto_record=None):
         self.model, self.criterion = model, criterion
-        # auto_record: the first call on a GPU batch records the step (record()), later calls of that shape replay it; other shapes, other
-        # criteria and ranks > 1 step eagerly.  Default: the SEPK_SEQUENCE switch (off unless SEPK_SEQUENCE=1).
+        # auto_record: the first call on a GPU batch records the step (record()), later calls of that shape replay it; other shapes and
+        # whatever recordable() names a reason for step eagerly.  Ranks > 1 of the fused family record too (the gradient buckets cut the
+        # list into segments, _seq_marks); the staged causal family records on a single rank.  Default: the SEPK_SEQUENCE switch (off
+        # unless SEPK_SEQUENCE=1).
         self.auto_record = (os.environ.get("SEPK_SEQUENCE", "0") == "1") if auto_record is None else bool(auto_record)
         self.lr, self.betas, self.eps, self.weight_decay, self.max_norm = lr, betas, eps, weight_decay, max_norm
         self.group = process_group
@@ -117,9 +121,12 @@ class FusedTrainStep:
         from criterion.sdr import SISDR, NegSISDR
         if self.comm and self.uneven:
             return "uneven_batches weights the loss by a count that is all-reduced under the forward pass: eager only"
-        if not getattr(self.model, "fused", False):
-            return "the recorded step is offered for the fused kernel sequence only; this model runs the {} path".format(
-                "derived-basis" if getattr(self.model, "fused_derived", False) else "staged" if getattr(self.model, "staged", False) else "composed")
+        staged = (not getattr(self.model, "fused", False)) and bool(getattr(self.model, "staged", False))
+        if not getattr(self.model, "fused", False) and not staged:
+            return "the recorded step is offered for the fused kernel sequence and the staged causal one; this model runs the {} path".format(
+                "derived-basis" if getattr(self.model, "fused_derived", False) else "composed")
+        if staged and self.comm:
+            return "the staged causal path records on a single rank; with a gradient exchange it steps eagerly"
         from criterion.pit import SinkPIT
         c = self.criterion
         pit_ok = isinstance(c, PIT) and type(c.criterion) in (SISDR, NegSISDR) and c.criterion.reduction in ("mean", "sum")
@@ -142,6 +149,7 @@ class FusedTrainStep:
         weight bound by sep_absmax, the tail of PIT (batch mean, gradient weights of the chosen permutation) by sep_pit_finish instead of
         torch kernels.  reference: egs/wsj0-mix/common/src/driver.py:141-157."""
         from . import net as _net
+        from . import causal as _causal
         from criterion.sdr import NegSISDR
         why = self.recordable()
         if why is not None:
@@ -150,6 +158,7 @@ class FusedTrainStep:
         K = sepkernels.backend()
         from criterion.pit import SinkPIT
         model, crit = self.model, self.criterion.criterion
+        drv = _net if model.fused else _causal          # the explicit forward / backward of the model's family; everything else is shared
         sink = type(self.criterion) is SinkPIT
         dev = self.flat.device
         B, n_src, T = sources.shape
@@ -197,7 +206,7 @@ class FusedTrainStep:
                 K.absmax(self.flat, amax, self.flat.numel())          # (alignment gaps of the flat buffer hold zeros)
             prev = sepkernels.set_weights_amax(amax)
             try:
-                est, _, sv = _net._forward(cfg, P, mix, False, True)
+                est, _, sv = drv._forward(cfg, P, mix, False, True)
                 est3 = est.view(B, n_src, T)
                 # PIT over the SI-SDR pair matrix (criterion/pit.py::_fused_pit, criterion/sdr.py::_SISDRPairsFn), launch for launch
                 dots = K.zeros(B, n_src, n_src, device=dev, dtype=torch.float64)
@@ -232,7 +241,7 @@ class FusedTrainStep:
                     pattern = Pm                                                 # (the soft assignment; last_pattern takes its argmax on demand)
                 d_est = torch.empty_like(est3)
                 K.sisdr_bwd(est3, src, dots, tt, xx, gw, d_est, B, n_src, T, True, crit.eps)
-                _net._backward(cfg, P, sv, d_est.view(B, n_src, 1, T), G, on_ready if bucketed else None, False)
+                drv._backward(cfg, P, sv, d_est.view(B, n_src, 1, T), G, on_ready if bucketed else None)
                 if bucketed:
                     bucket(0, starts[1] if R > 1 else total)
                 elif self.comm:

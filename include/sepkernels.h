@@ -589,6 +589,27 @@ int sep_online_advance(int64_t* frames, float* carry, const float* carry_next, i
 int sep_online_reset(const uint8_t* mask, int num_streams, int64_t* frames, float* carry, int carry_len, double* sums, int sums_len, float* rings,
                      int64_t rings_len, float* tail, int tail_len, sep_stream_t stream);
 
+/* ---- the causal TCN layer's first norm folded into its depthwise convolution (ABI 23, additive; csrc/causal.hip) ------------------------
+ * The first cLN of a causal layer (tdcn.py:107-147) feeds only the depthwise convolution, so its output v1 need not exist in memory:
+ *   sep_cln_stats                 sep_cln_fwd without the apply pass and without y: mean, rstd (B, ldt), bit for bit what sep_cln_fwd writes
+ *                                 (same ws, same alpha convention).
+ *   sep_depthwise_cln_fwd         y[b][c][t] = bias[c] + sum_k w[c][k] v1[b][c][t + k dil - pad] for t < T, zero for T <= t < ldt, with
+ *                                 v1[b][c][t'] = gamma[c] (PReLU(x[b][c][t']; alpha) - mean[b][t']) rstd[b][t'] + beta[c] for 0 <= t' < T and ZERO
+ *                                 outside (the reference pads after the norm).  x, y (B, C, ldt), ldt % 4 == 0; w (C, Kw); any Kw >= 1,
+ *                                 dil >= 1, 0 <= pad <= (Kw - 1) dil.  alpha and bias may be NULL.
+ *   sep_depthwise_cln_bwd_weight  partial[b][c][k] = sum_{t < T} dy[b][c][t] v1[b][c][t + k dil - pad] (k < Kw), partial[b][c][Kw] = sum_{t < T} dy:
+ *                                 sep_depthwise_bwd_weight with its x operand re-formed by the same prologue; to be added over b.
+ * The gradient at x needs nothing new: sep_depthwise_bwd_input yields d v1, sep_cln_bwd takes x, mean, rstd and alpha.
+ *   sep_sum_f64                   out[0] = sum_i x[i] over n floats, accumulated in fp64 in a fixed order: the (B, C) row partials of a PReLU
+ *                                 slope's gradient (sep_cln_bwd's dalpha_part) -> the one slope, inside a recorded step. */
+int sep_sum_f64(const float* x, int64_t n, float* out, sep_stream_t stream);
+int sep_cln_stats(const float* x, float* mean, float* rstd, double* ws, int B, int C, int T, int ldt, float eps, const float* alpha,
+                  sep_stream_t stream);
+int sep_depthwise_cln_fwd(const float* x, const float* alpha, const float* gamma, const float* beta, const float* mean, const float* rstd,
+                          const float* w, const float* bias, float* y, int B, int C, int T, int ldt, int Kw, int pad, int dil, sep_stream_t stream);
+int sep_depthwise_cln_bwd_weight(const float* dy, const float* x, const float* alpha, const float* gamma, const float* beta, const float* mean,
+                                 const float* rstd, float* partial, int B, int C, int T, int ldt, int Kw, int pad, int dil, sep_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

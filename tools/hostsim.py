@@ -17,7 +17,7 @@ import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dnn-based_source_separation_amd", "csrc")
-FILES = ("stream", "cln", "loss", "lstm", "linear", "attn", "rownorm", "gemm", "gemm_coop", "gemm_pc", "wgrad_pc", "wgrad_pc16", "sequence", "online")
+FILES = ("stream", "cln", "loss", "lstm", "linear", "attn", "rownorm", "gemm", "gemm_coop", "gemm_pc", "wgrad_pc", "wgrad_pc16", "sequence", "online", "causal")
 _DYN = re.compile(r"extern __shared__ (?:__attribute__\(\(aligned\(\d+\)\)\) )?(\w+) (\w+)\[\];")
 
 # The GEMM files: helper functions whose bodies are inline assembly (or address-space casts) get a C++ body in the compiled copies.
@@ -175,6 +175,15 @@ with hostsim.HostSimBackend({so!r}) as K:
             t0 = time.time()
             getattr(OG, name)(*p)
             print("  online {{:27s}} {{:28s}} {{:5.1f}} s".format(name, str(p)[:28], time.time() - t0), flush=True)
+    import test_causal_recorded_gpu as CG                                          # the folded causal entry points' cases (csrc/causal.hip, sep_cln_stats)
+    CG.HIP, CG.to_device, CG.device_sync, CG.device_name = K, (lambda t: t.clone()), (lambda: None), (lambda: "cpu")
+    for name, params in CG.CASES:
+        if only and not any(o in "causal_" + name for o in only):
+            continue
+        for p in params:
+            t0 = time.time()
+            getattr(CG, name)(*p)
+            print("  causal {{:27s}} {{:28s}} {{:5.1f}} s".format(name, str(p)[:28], time.time() - t0), flush=True)
     import sepkernels
     for arith, name, args in H.GEMM_CASES:
         if only and not any(o in name for o in only):
@@ -230,7 +239,8 @@ def run_case(argv):
 
 def main():
     """python tools/hostsim.py --asan | --tsan [--only NAMES] : the kernel cases of the CPU tier once more (tests/test_kernel_source_on_host_cpu.py
-    and the online cases of tests/test_online_gpu.py -- `--only online` selects those), with the kernel sources compiled under a
+    the online cases of tests/test_online_gpu.py -- `--only online` selects those -- and the folded causal cases of
+    tests/test_causal_recorded_gpu.py -- `--only causal`), with the kernel sources compiled under a
     sanitizer.  --asan: out-of-bounds reads / writes of global buffers (torch's allocations go through the intercepted allocator) and of
     the workgroup's LDS (function-local statics here) that happen to be harmless on the device.  --tsan: data races on LDS or global
     memory between the lanes of a workgroup -- a missing __syncthreads(), or code that silently relies on the lock-step of a wave (here
