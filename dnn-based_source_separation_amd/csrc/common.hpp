@@ -11,6 +11,8 @@
 
 // ---- error plumbing (thread-local, never throws across the ABI) -------------------
 void sep_set_error(const char* fmt, ...);
+// sep_last_kernel(): `name` is a string literal spelled by the launch macro / function that issues the launch (one pointer store)
+void sep_set_kernel(const char* name);
 
 #define SEP_REQUIRE(cond, ...)            \
     do {                                  \

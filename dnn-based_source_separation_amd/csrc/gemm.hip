@@ -1619,11 +1619,16 @@ extern "C" int sep_pw_gemm(const sep_gemm_desc* d, sep_stream_t stream) {
         const bool split6 = d->arith == SEP_ARITH_BF16X6 || d->arith == SEP_ARITH_F16X3;
 #define SEP_LD(T, P, S, E)                                                                                                                           \
     do {                                                                                                                                             \
-        if (split3 && P != SEP_PRO_GLN_BWD)                                                                                                          \
+        if (split3 && P != SEP_PRO_GLN_BWD) {                                                                                                        \
+            sep_set_kernel("direct<" #T "," #P "," #S "," #E ",arith=2>");                                                                           \
             hipLaunchKernelGGL((pw_gemm_direct_kernel<T, P, S, E, (P != SEP_PRO_GLN_BWD ? 2 : 0)>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d); \
-        else if (split6 && P != SEP_PRO_GLN_BWD)                                                                                                     \
+        } else if (split6 && P != SEP_PRO_GLN_BWD) {                                                                                                 \
+            sep_set_kernel("direct<" #T "," #P "," #S "," #E ",arith=1>");                                                                           \
             hipLaunchKernelGGL((pw_gemm_direct_kernel<T, P, S, E, (P != SEP_PRO_GLN_BWD ? 1 : 0)>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d); \
-        else hipLaunchKernelGGL((pw_gemm_direct_kernel<T, P, S, E, 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);                          \
+        } else {                                                                                                                                     \
+            sep_set_kernel("direct<" #T "," #P "," #S "," #E ",arith=0>");                                                                           \
+            hipLaunchKernelGGL((pw_gemm_direct_kernel<T, P, S, E, 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);                           \
+        }                                                                                                                                            \
     } while (0)
         // 1. the (operand form, prologue, split, epilogue) combinations of the Conv-TasNet step, epilogue flags compile-time
         const int ef = d->epi_flags, pm = d->pro_mode;
@@ -1649,11 +1654,16 @@ extern "C" int sep_pw_gemm(const sep_gemm_desc* d, sep_stream_t stream) {
         else done = false;
         // 2. anything else: same kernels with the flags read at run time
         if (!done) {
-#define SEP_LG(T, P, S) hipLaunchKernelGGL((pw_gemm_direct_kernel<T, P, S, -1, 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d)
-#define SEP_LAUNCH_DIRECT(T, P)               \
-    do {                                      \
-        if (sp) SEP_LG(T, P, true);           \
-        else SEP_LG(T, P, false);             \
+            // (NAME: the arguments as the caller spelled them -- macro arguments that pass through SEP_LAUNCH_DIRECT arrive here expanded)
+#define SEP_LG(T, P, S, NAME)                                                                                                     \
+    do {                                                                                                                          \
+        sep_set_kernel("direct_rt<" NAME "," #S ">");                                                                             \
+        hipLaunchKernelGGL((pw_gemm_direct_kernel<T, P, S, -1, 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);            \
+    } while (0)
+#define SEP_LAUNCH_DIRECT(T, P)                       \
+    do {                                              \
+        if (sp) SEP_LG(T, P, true, #T "," #P);        \
+        else SEP_LG(T, P, false, #T "," #P);          \
     } while (0)
             switch (pm * 2 + (tr ? 1 : 0)) {
                 case 0: SEP_LAUNCH_DIRECT(false, SEP_PRO_NONE); break;
@@ -1664,15 +1674,17 @@ extern "C" int sep_pw_gemm(const sep_gemm_desc* d, sep_stream_t stream) {
                 case 5: SEP_LAUNCH_DIRECT(true, SEP_PRO_GLN); break;
                 case 6: SEP_LAUNCH_DIRECT(false, SEP_PRO_GLN_PRELU); break;
                 case 7: SEP_LAUNCH_DIRECT(true, SEP_PRO_GLN_PRELU); break;
-                case 8: SEP_LG(false, SEP_PRO_GLN_BWD, false); break;
-                default: SEP_LG(true, SEP_PRO_GLN_BWD, false); break;
+                case 8: SEP_LG(false, SEP_PRO_GLN_BWD, false, "false,SEP_PRO_GLN_BWD"); break;
+                default: SEP_LG(true, SEP_PRO_GLN_BWD, false, "true,SEP_PRO_GLN_BWD"); break;
             }
 #undef SEP_LAUNCH_DIRECT
 #undef SEP_LG
         }
 #undef SEP_LD
-    } else
+    } else {
+        sep_set_kernel("staged");
         hipLaunchKernelGGL(pw_gemm_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);
+    }
     SEP_CHECK_LAUNCH("sep_pw_gemm");
     return 0;
 }
@@ -1705,21 +1717,29 @@ extern "C" int sep_pw_wgrad(const sep_wgrad_desc* d, sep_stream_t stream) {
         return 0;
     }
     if (direct_ok && d->arith != SEP_ARITH_F32) {      // F16X3: the weight gradient stays on the bf16 split (both operands are activations)
+#define SEP_LWG(KERNEL, FAMILY, XM, THREADS)                                                                    \
+    do {                                                                                                        \
+        sep_set_kernel(FAMILY "<" #XM ">");                                                                     \
+        hipLaunchKernelGGL((KERNEL<XM>), dim3(grid), dim3(THREADS), 0, (hipStream_t)stream, *d);                \
+    } while (0)
         switch (d->x_mode) {
-            case SEP_PRO_NONE: hipLaunchKernelGGL((pw_wgrad_split_kernel<SEP_PRO_NONE>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d); break;
-            case SEP_PRO_PRELU: hipLaunchKernelGGL((pw_wgrad_split_kernel<SEP_PRO_PRELU>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d); break;
-            case SEP_PRO_GLN: hipLaunchKernelGGL((pw_wgrad_split_kernel<SEP_PRO_GLN>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d); break;
-            default: hipLaunchKernelGGL((pw_wgrad_split_kernel<SEP_PRO_GLN_PRELU>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d); break;
+            case SEP_PRO_NONE: SEP_LWG(pw_wgrad_split_kernel, "wgrad_split", SEP_PRO_NONE, 256); break;
+            case SEP_PRO_PRELU: SEP_LWG(pw_wgrad_split_kernel, "wgrad_split", SEP_PRO_PRELU, 256); break;
+            case SEP_PRO_GLN: SEP_LWG(pw_wgrad_split_kernel, "wgrad_split", SEP_PRO_GLN, 256); break;
+            default: SEP_LWG(pw_wgrad_split_kernel, "wgrad_split", SEP_PRO_GLN_PRELU, 256); break;
         }
     } else if (direct_ok) {
         switch (d->x_mode) {
-            case SEP_PRO_NONE: hipLaunchKernelGGL((pw_wgrad_direct_kernel<SEP_PRO_NONE>), dim3(grid), dim3(512), 0, (hipStream_t)stream, *d); break;
-            case SEP_PRO_PRELU: hipLaunchKernelGGL((pw_wgrad_direct_kernel<SEP_PRO_PRELU>), dim3(grid), dim3(512), 0, (hipStream_t)stream, *d); break;
-            case SEP_PRO_GLN: hipLaunchKernelGGL((pw_wgrad_direct_kernel<SEP_PRO_GLN>), dim3(grid), dim3(512), 0, (hipStream_t)stream, *d); break;
-            default: hipLaunchKernelGGL((pw_wgrad_direct_kernel<SEP_PRO_GLN_PRELU>), dim3(grid), dim3(512), 0, (hipStream_t)stream, *d); break;
+            case SEP_PRO_NONE: SEP_LWG(pw_wgrad_direct_kernel, "wgrad_direct", SEP_PRO_NONE, 512); break;
+            case SEP_PRO_PRELU: SEP_LWG(pw_wgrad_direct_kernel, "wgrad_direct", SEP_PRO_PRELU, 512); break;
+            case SEP_PRO_GLN: SEP_LWG(pw_wgrad_direct_kernel, "wgrad_direct", SEP_PRO_GLN, 512); break;
+            default: SEP_LWG(pw_wgrad_direct_kernel, "wgrad_direct", SEP_PRO_GLN_PRELU, 512); break;
         }
-    } else
+#undef SEP_LWG
+    } else {
+        sep_set_kernel("wgrad");
         hipLaunchKernelGGL(pw_wgrad_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);
+    }
     SEP_CHECK_LAUNCH("sep_pw_wgrad");
     return 0;
 }

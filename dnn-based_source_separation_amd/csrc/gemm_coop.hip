@@ -453,10 +453,11 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const PackArgs a) {
 }
 
 template <int MI, int PRO, bool SPLIT, int EF>
-void launch_coop(const sep_gemm_desc& d, const int ns, hipStream_t stream) {
+void launch_coop(const sep_gemm_desc& d, const int ns, hipStream_t stream, const char* name_ns2, const char* name_ns3) {
     const int NR = d.M / (128 * MI);
     const int NC = d.B * (d.ldt / CBN);
     const int grid = 8 * NR * ceil_div(NC, 8);
+    sep_set_kernel(ns == 3 ? name_ns3 : name_ns2);                             // sep_last_kernel(): spelled by SEP_LC / SEP_LC4 from the arguments they instantiate
     if (ns == 3) hipLaunchKernelGGL((pw_gemm_coop_kernel<MI, PRO, SPLIT, EF, 3>), dim3(grid), dim3(256), 0, stream, d);
     else hipLaunchKernelGGL((pw_gemm_coop_kernel<MI, PRO, SPLIT, EF, 2>), dim3(grid), dim3(256), 0, stream, d);
 }
@@ -498,14 +499,21 @@ int sep_pw_gemm_packed(const sep_gemm_desc* d, hipStream_t stream) {
     // Measured, recorded sequence (profiles/r08f_kernel_choice_toggles.txt, r08g_coop_tile_per_shape.txt): none 15.29, conv1 15.33, heads^T 15.19, all 15.22 ms per step
     // (means of three alternating runs on one box).
     static const int mi4 = force_mi == 4 ? 7 : getenv("SEPK_COOP_MI4") ? atoi(getenv("SEPK_COOP_MI4")) : SEP_COOP_MI4_DEFAULT;
-    if ((mi4 & 1) && force_mi != 1 && force_mi != 2 && d->M % 512 == 0 && !sp && pm == SEP_PRO_NONE && ef == SEP_EPI_STATS_PRELU) { launch_coop<4, SEP_PRO_NONE, false, SEP_EPI_STATS_PRELU>(*d, ns, stream); return 1; }
-    if ((mi4 & 2) && force_mi != 1 && force_mi != 2 && d->M % 512 == 0 && sp && pm == SEP_PRO_NONE && ef == 0) { launch_coop<4, SEP_PRO_NONE, true, 0>(*d, ns, stream); return 1; }
-    if ((mi4 & 4) && force_mi != 1 && force_mi != 2 && d->M % 512 == 0 && !sp && pm == SEP_PRO_NONE && ef == 0) { launch_coop<4, SEP_PRO_NONE, false, 0>(*d, ns, stream); return 1; }
-#define SEP_LC(P, S, E)                                              \
-    do {                                                             \
-        if (mi == 2) launch_coop<2, P, S, E>(*d, ns, stream);        \
-        else launch_coop<1, P, S, E>(*d, ns, stream);                \
-        return 1;                                                    \
+#define SEP_CN(MI, TAIL) "coop<" MI "," TAIL ",ns=2>", "coop<" MI "," TAIL ",ns=3>"
+#define SEP_LC4(P, S, E)                                                                    \
+    do {                                                                                    \
+        launch_coop<4, P, S, E>(*d, ns, stream, SEP_CN("4", #P "," #S "," #E));             \
+        return 1;                                                                           \
+    } while (0)
+    if ((mi4 & 1) && force_mi != 1 && force_mi != 2 && d->M % 512 == 0 && !sp && pm == SEP_PRO_NONE && ef == SEP_EPI_STATS_PRELU) SEP_LC4(SEP_PRO_NONE, false, SEP_EPI_STATS_PRELU);
+    if ((mi4 & 2) && force_mi != 1 && force_mi != 2 && d->M % 512 == 0 && sp && pm == SEP_PRO_NONE && ef == 0) SEP_LC4(SEP_PRO_NONE, true, 0);
+    if ((mi4 & 4) && force_mi != 1 && force_mi != 2 && d->M % 512 == 0 && !sp && pm == SEP_PRO_NONE && ef == 0) SEP_LC4(SEP_PRO_NONE, false, 0);
+#undef SEP_LC4
+#define SEP_LC(P, S, E)                                                                                 \
+    do {                                                                                                \
+        if (mi == 2) launch_coop<2, P, S, E>(*d, ns, stream, SEP_CN("2", #P "," #S "," #E));            \
+        else launch_coop<1, P, S, E>(*d, ns, stream, SEP_CN("1", #P "," #S "," #E));                    \
+        return 1;                                                                                       \
     } while (0)
     // the (prologue, two-source contraction, epilogue) combinations of the Conv-TasNet step, epilogue flags compile-time
     if (!sp && pm == SEP_PRO_NONE && ef == SEP_EPI_STATS_PRELU) SEP_LC(SEP_PRO_NONE, false, SEP_EPI_STATS_PRELU);                      // TCN conv1
@@ -523,6 +531,7 @@ int sep_pw_gemm_packed(const sep_gemm_desc* d, hipStream_t stream) {
     if (!sp && pm == SEP_PRO_GLN_BWD && ef == SEP_EPI_RESIDUAL) SEP_LC(SEP_PRO_GLN_BWD, false, SEP_EPI_RESIDUAL);                     // conv1^T
     if (!sp && pm == SEP_PRO_GLN_BWD && ef == 0) SEP_LC(SEP_PRO_GLN_BWD, false, 0);
 #undef SEP_LC
+#undef SEP_CN
     return 0;
 }
 

@@ -577,7 +577,7 @@ __global__ __launch_bounds__(512, 2) void pw_gemm_pc_kernel(const sep_gemm_desc 
 }
 
 template <int WR, int WC, int PRO, bool SPLIT, int EF>
-void launch_pcd(const sep_gemm_desc& d, hipStream_t stream) {
+void launch_pcd(const sep_gemm_desc& d, hipStream_t stream, const char* name) {
     constexpr bool BWD = PRO == SEP_PRO_GLN_BWD;
     // ring depths: raw ring NS (DMA prefetch distance NS - 1 chunks), operand ring NB (how far the producers may run ahead); the
     // producer loop is unrolled over lcm(NS, NB) chunks
@@ -586,6 +586,7 @@ void launch_pcd(const sep_gemm_desc& d, hipStream_t stream) {
     const int NR = d.M / (64 * WR);
     const int NC = d.B * (d.ldt / (128 * WC));
     const int grid = 8 * NR * ceil_div(NC, 8);
+    sep_set_kernel(name);                                                      // sep_last_kernel(): spelled by SEP_LP from the arguments it instantiates
     hipLaunchKernelGGL((pw_gemm_pc_kernel<WR, WC, PRO, SPLIT, EF, NS, NB>), dim3(grid), dim3(512), 0, stream, d);
 }
 
@@ -600,11 +601,11 @@ int sep_pw_gemm_pc(const sep_gemm_desc* d, hipStream_t stream) {
     const int ef = d->epi_flags, pm = d->pro_mode;
     const bool sp = d->k_split != 0;
     const bool tall = d->M % 256 == 0 && !force_22;      // 256 x 128 tile (consumers 4 x 1), else 128 x 256 (2 x 2)
-#define SEP_LP(P, S, E)                                          \
-    do {                                                         \
-        if (tall) launch_pcd<4, 1, P, S, E>(*d, stream);         \
-        else launch_pcd<2, 2, P, S, E>(*d, stream);              \
-        return 1;                                                \
+#define SEP_LP(P, S, E)                                                                          \
+    do {                                                                                         \
+        if (tall) launch_pcd<4, 1, P, S, E>(*d, stream, "pc<4,1," #P "," #S "," #E ">");         \
+        else launch_pcd<2, 2, P, S, E>(*d, stream, "pc<2,2," #P "," #S "," #E ">");              \
+        return 1;                                                                                \
     } while (0)
     if (!sp && pm == SEP_PRO_NONE && ef == SEP_EPI_STATS_PRELU) SEP_LP(SEP_PRO_NONE, false, SEP_EPI_STATS_PRELU);                      // TCN conv1
     if (!sp && pm == SEP_PRO_GLN_PRELU && ef == SEP_EPI_RESIDUAL) SEP_LP(SEP_PRO_GLN_PRELU, false, SEP_EPI_RESIDUAL);                 // heads

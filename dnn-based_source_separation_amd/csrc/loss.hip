@@ -462,4 +462,7 @@ void sep_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* sep_last_error(void) { return g_err; }
+static thread_local const char* g_kernel = "";
+void sep_set_kernel(const char* name) { g_kernel = name; }
+extern "C" const char* sep_last_kernel(void) { return g_kernel; }
 extern "C" int sep_version(void) { return SEP_ABI_VERSION; }

@@ -426,12 +426,13 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc_kernel(const sep_wgrad_des
 }
 
 template <int WR, int WC, int XMODE>
-void launch_wpc(const sep_wgrad_desc& d, hipStream_t stream) {
+void launch_wpc(const sep_wgrad_desc& d, hipStream_t stream, const char* name) {
     const int ntiles = (d.M / (64 * WR)) * (d.N / (128 * WC));
     const int grid = 8 * ntiles * ceil_div(d.nsplit, 8);
     // raw-ring depth NS (SEPK_WPC_NS = 2 | 3 | 4 for A/B runs): 4 = chunks fetched in pairs (one HBM fetch per 128-byte line), 2 / 3 = one
     // chunk per barrier, a DMA has NS - 1 chunk periods to land
     static const int ns = getenv("SEPK_WPC_NS") ? atoi(getenv("SEPK_WPC_NS")) : 4;
+    sep_set_kernel(name);                                                      // sep_last_kernel() (the ring depth is not part of the name)
     if (ns == 4) hipLaunchKernelGGL((pw_wgrad_pc_kernel<WR, WC, XMODE, 4>), dim3(grid), dim3(512), 0, stream, d);
     else if (ns == 3) hipLaunchKernelGGL((pw_wgrad_pc_kernel<WR, WC, XMODE, 3>), dim3(grid), dim3(512), 0, stream, d);
     else hipLaunchKernelGGL((pw_wgrad_pc_kernel<WR, WC, XMODE, 2>), dim3(grid), dim3(512), 0, stream, d);
@@ -450,8 +451,8 @@ int sep_pw_wgrad_pc(const sep_wgrad_desc* d, hipStream_t stream) {
     if ((long)d->nsplit > (long)d->B * (d->ldt / DK)) return 0;
 #define SEP_LW(XM)                                           \
     do {                                                     \
-        if (tall) launch_wpc<4, 1, XM>(*d, stream);          \
-        else launch_wpc<2, 2, XM>(*d, stream);               \
+        if (tall) launch_wpc<4, 1, XM>(*d, stream, "wgrad_pc<4,1," #XM ">"); \
+        else launch_wpc<2, 2, XM>(*d, stream, "wgrad_pc<2,2," #XM ">");      \
         return 1;                                            \
     } while (0)
     switch (d->x_mode) {

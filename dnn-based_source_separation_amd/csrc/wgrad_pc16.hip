@@ -637,14 +637,16 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc16_batch_kernel(const W16Ba
 }
 
 template <int WR, int WC, int XMODE, bool G2PRE = false>
-void launch_w16(const sep_wgrad_desc& d, hipStream_t stream) {
+void launch_w16(const sep_wgrad_desc& d, hipStream_t stream, const char* name) {
     const int ntiles = (d.M / (64 * WR)) * (d.N / (128 * WC));
     const int grid = 8 * ntiles * ceil_div(d.nsplit, 8);
+    sep_set_kernel(name);                                                      // sep_last_kernel()
     hipLaunchKernelGGL((pw_wgrad_pc16_kernel<WR, WC, XMODE, G2PRE>), dim3(grid), dim3(512), 0, stream, d);
 }
 
 template <int WR, int WC, int XMODE>
-void launch_w16_batch(const W16Batch& b, int n, hipStream_t stream) {
+void launch_w16_batch(const W16Batch& b, int n, hipStream_t stream, const char* name) {
+    sep_set_kernel(name);                                                      // sep_last_kernel()
     hipLaunchKernelGGL((pw_wgrad_pc16_batch_kernel<WR, WC, XMODE>), dim3(n * b.per), dim3(512), 0, stream, b);
 }
 
@@ -670,13 +672,13 @@ int sep_pw_wgrad_pc16(const sep_wgrad_desc* d, hipStream_t stream) {
             return 0;
         sep_wgrad_desc q = *d;
         q.G2 = reinterpret_cast<const float*>(d->G2_pre);      // same row pitch and line size as the fp32 tensor: the DMA does not change
-        if (d->x_mode == SEP_PRO_PRELU) launch_w16<4, 1, SEP_PRO_PRELU, true>(q, stream);
-        else launch_w16<4, 1, SEP_PRO_NONE, true>(q, stream);
+        if (d->x_mode == SEP_PRO_PRELU) launch_w16<4, 1, SEP_PRO_PRELU, true>(q, stream, "wgrad_pc16_pre<4,1,SEP_PRO_PRELU>");
+        else launch_w16<4, 1, SEP_PRO_NONE, true>(q, stream, "wgrad_pc16_pre<4,1,SEP_PRO_NONE>");
         return 1;
     }
 #define SEP_LW(XM)                                           \
     do {                                                     \
-        launch_w16<4, 1, XM>(*d, stream);                    \
+        launch_w16<4, 1, XM>(*d, stream, "wgrad_pc16<4,1," #XM ">"); \
         return 1;                                            \
     } while (0)
     switch (d->x_mode) {
@@ -711,10 +713,10 @@ int sep_pw_wgrad_pc16_batch(const sep_wgrad_desc* ds, int n, hipStream_t stream)
         b.G[k] = q.G; b.G2[k] = q.G2; b.X[k] = q.X; b.partial[k] = q.partial; b.partial_bias[k] = q.partial_bias;
     }
     switch (ds[0].x_mode) {
-        case SEP_PRO_NONE: launch_w16_batch<4, 1, SEP_PRO_NONE>(b, n, stream); break;
-        case SEP_PRO_PRELU: launch_w16_batch<4, 1, SEP_PRO_PRELU>(b, n, stream); break;
-        case SEP_PRO_GLN: launch_w16_batch<4, 1, SEP_PRO_GLN>(b, n, stream); break;
-        default: launch_w16_batch<4, 1, SEP_PRO_GLN_PRELU>(b, n, stream); break;
+        case SEP_PRO_NONE: launch_w16_batch<4, 1, SEP_PRO_NONE>(b, n, stream, "wgrad_pc16_batch<4,1,SEP_PRO_NONE>"); break;
+        case SEP_PRO_PRELU: launch_w16_batch<4, 1, SEP_PRO_PRELU>(b, n, stream, "wgrad_pc16_batch<4,1,SEP_PRO_PRELU>"); break;
+        case SEP_PRO_GLN: launch_w16_batch<4, 1, SEP_PRO_GLN>(b, n, stream, "wgrad_pc16_batch<4,1,SEP_PRO_GLN>"); break;
+        default: launch_w16_batch<4, 1, SEP_PRO_GLN_PRELU>(b, n, stream, "wgrad_pc16_batch<4,1,SEP_PRO_GLN_PRELU>"); break;
     }
     return 1;
 }

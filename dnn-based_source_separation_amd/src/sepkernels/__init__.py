@@ -127,6 +127,7 @@ _I, _F, _D, _L = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_int64
 SIGNATURES = {
     "sep_version": [],
     "sep_last_error": [],
+    "sep_last_kernel": [],
     "sep_pw_gemm": [ctypes.POINTER(GemmDesc), _vp],
     "sep_pack_weights": [ctypes.POINTER(PackSeg), _I, _vp],
     "sep_pw_wgrad": [ctypes.POINTER(WgradDesc), _vp],
@@ -209,7 +210,7 @@ SIGNATURES = {
     "sep_depthwise_cln_bwd_weight": [_vp] * 8 + [_I] * 7 + [_vp],
     "sep_sum_f64": [_vp, _L, _vp, _vp],
 }
-_RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
+_RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_last_kernel": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
              "sep_gln_tokens_ws_bytes": ctypes.c_size_t}
 
 _lib = None
@@ -381,6 +382,12 @@ def _stream():
 def _check(rc, name):
     if rc != 0:
         raise SepKernelsError("{} failed ({}): {}".format(name, rc, load().sep_last_error().decode()))
+
+
+def last_kernel():
+    """Name of the kernel instance this thread's last pw_gemm / pw_wgrad / pw_wgrad_batch launch went to (sep_last_kernel: family and
+    template arguments, e.g. 'pc<4,1,SEP_PRO_GLN_PRELU,false,SEP_EPI_RESIDUAL>'), '' before the first one.  Not a launch: never recorded."""
+    return load().sep_last_kernel().decode()
 
 
 _f32, _f64 = torch.float32, torch.float64

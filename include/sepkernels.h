@@ -39,6 +39,18 @@ typedef void* sep_stream_t; /* hipStream_t */
 
 int sep_version(void);
 const char* sep_last_error(void);
+/* Which kernel instance the calling thread's last sep_pw_gemm / sep_pw_wgrad / sep_pw_wgrad_batch launch went to: a string literal
+ * naming the family and the template arguments as the dispatcher spells them, "" before the first such launch.  The families:
+ *   pc<WR,WC,prologue,two-source,epilogue>         producer / consumer kernel, packed weights (csrc/gemm_pc.hip)
+ *   coop<MI,prologue,two-source,epilogue,ns=N>     cooperative kernel, packed weights (csrc/gemm_coop.hip)
+ *   direct<trans_a,prologue,two-source,epilogue,arith=A>   per-wave kernel, flags compile-time (csrc/gemm.hip)
+ *   direct_rt<trans_a,prologue,two-source>         the same kernel with the epilogue flags read at run time
+ *   staged                                         register-staged fallback
+ *   wgrad_pc16<..> / wgrad_pc16_pre<..> / wgrad_pc16_batch<..> / wgrad_pc<..> / wgrad_split<..> / wgrad_direct<..> / wgrad
+ * e.g. "pc<4,1,SEP_PRO_GLN_PRELU,false,SEP_EPI_RESIDUAL>".  Thread-local like sep_last_error; one pointer store per launch, no device
+ * work; takes no stream, so it is not a sequence op.  For tests and tools that must know which instance a shape reaches
+ * (tests/gemm_matrix.py); additive to ABI 23. */
+const char* sep_last_kernel(void);
 
 /* ---- prologue modes applied to the X operand while it is staged into LDS ---------- */
 #define SEP_PRO_NONE 0

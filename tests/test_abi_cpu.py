@@ -65,7 +65,7 @@ def test_sequence_table_covers_every_entry_point_that_takes_a_stream():
         assert lib.sep_seq_nargs(k) == len(decls[n].split(",")) - 1 == len(sepkernels.SIGNATURES[n]) - 1, n
         assert lib.sep_seq_nargs(k) <= sepkernels.SEQ_MAX_ARGS
     assert ids == set(range(len(with_stream)))
-    for n in ("sep_version", "sep_last_error", "sep_cln_ws_bytes", "sep_run_sequence", "nonsense"):
+    for n in ("sep_version", "sep_last_error", "sep_last_kernel", "sep_cln_ws_bytes", "sep_run_sequence", "nonsense"):
         assert lib.sep_seq_lookup(n.encode()) == -1
     assert ctypes.sizeof(sepkernels.SeqArg) == 8 and sepkernels.SeqOp.args.offset == 8
     assert ctypes.sizeof(sepkernels.SeqOp) == 8 + 8 * sepkernels.SEQ_MAX_ARGS
@@ -94,6 +94,7 @@ def test_recording_proxy_marshals_arguments_by_signature():
     with sepkernels.recording(seq):
         rec = sepkernels.load()
         assert rec.sep_version() == 23                                       # not a launch: passed through
+        assert rec.sep_last_kernel() == sepkernels.last_kernel().encode()    # neither is the kernel-name observable (no stream)
         assert rec.sep_pw_gemm(ctypes.byref(d), None) < 0                    # a failing call is not recorded
         assert rec.sep_memset(None, 0, 0, None) == 0
         with pytest.raises(sepkernels.SepKernelsError):

@@ -1,0 +1,92 @@
+"""CPU: every kernel instance sep_pw_gemm can launch, reached BY NAME on the host simulation of the kernel sources and compared with a
+float64 restatement of the call's contract in the error model's own metric (tests/gemm_matrix.py: the ledger, the case matrix, the
+reference and the bound).  One child process per environment -- the dispatchers read their SEPK_* switches once per process."""
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import hostsim                         # noqa: E402
+import gemm_matrix as GM               # noqa: E402
+
+pytestmark = pytest.mark.skipif(hostsim.compiler() is None, reason="needs clang++ (ext_vector_type)")
+
+
+@pytest.fixture(scope="module")
+def sim_library(tmp_path_factory):
+    return hostsim.build(str(tmp_path_factory.mktemp("hostsim_gemm")))
+
+
+@pytest.fixture(scope="module")
+def reached():
+    """instance names the environments' children reported, filled in by the per-environment test below"""
+    return {}
+
+
+@pytest.mark.parametrize("env", list(GM.ENVS))
+def test_every_instance_of_the_environment_is_reached_and_within_its_bound(sim_library, reached, tmp_path, env):
+    out = str(tmp_path / "records.json")
+    argv, penv = GM.child_command(env, "host", out, backend="hostsim:" + sim_library)
+    r = subprocess.run(argv, env=penv, capture_output=True, text=True, timeout=3600)
+    assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-3000:]
+    recs = json.load(open(out))
+    assert len(recs) == len(GM.cases(env, "host"))
+    assert not GM.failures(recs)
+    for rec in recs:
+        assert rec["kernel"] == rec["case"]["name"], rec                 # the case reached the instance it names
+        assert rec["pads_zero"] and rec["inputs_intact"] and rec["guards_intact"], rec
+        for name, o in rec["outputs"].items():
+            assert o["err"] <= o["bound"], (rec["kernel"], name, o)
+    names = set(rec["kernel"] for rec in recs)
+    assert names >= set(GM.ENV_INSTANCES[env]), sorted(set(GM.ENV_INSTANCES[env]) - names)
+    reached[env] = names
+
+
+def test_the_union_over_the_environments_is_the_ledger(reached):
+    """no instance of the dispatch tables unreached, no name emitted that the ledger does not know (needs the per-environment runs above)"""
+    assert sorted(reached) == sorted(GM.ENVS), "an environment's run is missing: {}".format(sorted(set(GM.ENVS) - set(reached)))
+    union = set().union(*reached.values())
+    assert sorted(union) == GM.INSTANCES, (sorted(set(GM.INSTANCES) - union), sorted(union - set(GM.INSTANCES)))
+
+
+def test_the_ledger_lists_every_launch_line_of_the_dispatchers():
+    """INSTANCES against the sources: one SEP_LP / SEP_LC / SEP_LC4 / SEP_LD line or SEP_LAUNCH_DIRECT case per combination"""
+    csrc = os.path.join(ROOT, "dnn-based_source_separation_amd", "csrc")
+    count = lambda f, *calls: sum(open(os.path.join(csrc, f)).read().count(c) for c in calls)
+    assert count("gemm_pc.hip", "SEP_LP(SEP_PRO_") == len(GM.PACKED_COMBOS) == 14
+    assert count("gemm_coop.hip", "SEP_LC(SEP_PRO_") == 14 and count("gemm_coop.hip", "SEP_LC4(SEP_PRO_") == len(GM.COOP_MI4) == 3
+    assert count("gemm.hip", "SEP_LD(false, SEP_PRO_", "SEP_LD(true, SEP_PRO_") == len(GM.DIRECT_COMBOS) == 16
+    assert 2 * count("gemm.hip", "SEP_LAUNCH_DIRECT(false, SEP_PRO_", "SEP_LAUNCH_DIRECT(true, SEP_PRO_") + \
+        count("gemm.hip", "SEP_LG(false, SEP_PRO_", "SEP_LG(true, SEP_PRO_") == len(GM.DIRECT_RT_ALL) == 18
+    assert len(GM.INSTANCES) == 28 + 2 * (28 + 3) + (14 * 3 + 2) + 18 + 1
+
+
+def _one_case(sim_library, perturb):
+    import sepkernels
+    c = dict(GM.cases("default", "host")[1])          # the heads' form on the producer / consumer kernel
+    assert c["name"] == "pc<4,1,SEP_PRO_GLN_PRELU,false,SEP_EPI_RESIDUAL>"
+    with hostsim.HostSimBackend(sim_library) as K:
+        return GM.run_case(K, c, (lambda t: t.clone()), (lambda: None), perturb=perturb)
+
+
+def test_the_bound_rejects_a_result_off_by_2_to_the_minus_14_of_the_scale(sim_library):
+    """numerical control of the checker: a dropped hi*lo cross term is ~2^-11 of the scale; a device result perturbed by 2^-14 of it must
+    already fail, the unperturbed one passes (the in-process dispatch is the default environment's)"""
+    for k in GM.SWITCHES:
+        assert k not in os.environ
+    good = _one_case(sim_library, 0.0)
+    assert good["ok"] and good["outputs"]["Y"]["err"] <= good["outputs"]["Y"]["bound"] < 2.0 ** -16, good
+    bad = _one_case(sim_library, 2.0 ** -14)
+    assert not bad["ok"] and bad["outputs"]["Y"]["err"] > bad["outputs"]["Y"]["bound"], bad
+    assert bad["kernel"] == good["kernel"] and bad["pads_zero"] and bad["inputs_intact"]
+
+
+def test_a_gln_prologue_beyond_the_affine_tables_is_refused_or_staged():
+    """K = 528 behind a gLN prologue: no family takes it (the packed kernels and the direct kernel hold 512 table rows, the register-staged
+    fallback needs K % 32 == 0) and the call is refused with a message, not launched somewhere else; K = 544 runs on the fallback"""
+    got = {c["K"]: c["name"] for c in GM.cases("default", "device") if c["regime"] in ("gln528", "gln544") and c["packed"]}
+    assert got == {528: "error", 544: "staged"}

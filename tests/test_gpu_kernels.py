@@ -3,6 +3,7 @@ emulation (tests/emulator.py) on identical seeded buffers.  The emulator itself 
 reference golden vectors by the CPU tests, so agreement here chains each HIP kernel to the reference.
 Pure outputs are pre-filled with NaN so that an element the kernel forgets to write is caught."""
 import itertools
+import os
 
 import pytest
 import torch
@@ -264,13 +265,37 @@ def test_gemm_dgrad_two_sources_plain(H, T, arith):
     both("pw_gemm", [], kw)
 
 
-def test_gemm_dgrad_prelu_bwd(arith):
-    B, M, K, T = 2, 64, 384, 333
-    ldt = 384
+def _gemm_dgrad_prelu_bwd(B, M, K, T, ldt):
     Wm = rnd(K, M, scale=0.1)
     dpre, S = padded(B, K, T, ldt), padded(B, M, T, ldt)
     both("pw_gemm", [], dict(B=B, M=M, K=K, T=T, ldt=ldt, trans_a=1, A=Wm, X=dpre, Y=nan(B, M, ldt), epi_flags=EPI_PRELU_BWD,
                              epi_aux=S, epi_alpha=torch.tensor([0.25]), epi_dalpha=torch.zeros(1, dtype=torch.float64)))
+
+
+def test_gemm_dgrad_prelu_bwd(arith):
+    _gemm_dgrad_prelu_bwd(2, 64, 384, 333, 384)
+
+
+def _assert_instance(prefix):
+    """with packed weights and the default dispatch (no SEPK_* switch in the process), the last launch went to the named family"""
+    import gemm_matrix
+    if PACKED[0] and not any(k in os.environ for k in gemm_matrix.SWITCHES):
+        assert sepkernels.last_kernel().startswith(prefix), sepkernels.last_kernel()
+
+
+def test_gemm_dgrad_prelu_bwd_long_contraction(arith):
+    """mask^T at a shape the producer / consumer kernel takes (K >= 512, ldt % 256 == 0, M % 128 == 0): its PRELU_BWD instance"""
+    _gemm_dgrad_prelu_bwd(2, 128, 512, 500, 512)
+    _assert_instance("pc<2,2,SEP_PRO_NONE,false,SEP_EPI_PRELU_BWD>")
+
+
+def test_gemm_stats_epilogue_long_contraction(arith):
+    """the PReLU-statistics epilogue behind a K = 512 contraction: the producer / consumer kernel's STATS_PRELU instance with packed weights"""
+    B, M, K, T, ldt = 2, 256, 512, 500, 512
+    X, A, bias = padded(B, K, T, ldt), rnd(M, K, scale=K ** -0.5), rnd(M)
+    both("pw_gemm", [], dict(B=B, M=M, K=K, T=T, ldt=ldt, A=A, X=X, Y=nan(B, M, ldt), bias=bias, epi_flags=EPI_STATS_PRELU,
+                             epi_alpha=torch.tensor([0.25]), epi_stats=zstats(B), eps=1e-12))
+    _assert_instance("pc<4,1,SEP_PRO_NONE,false,SEP_EPI_STATS_PRELU>")
 
 
 @pytest.mark.parametrize("residual", [0, 1])
@@ -343,6 +368,7 @@ def test_gemm_packed_weights_model_shapes(M, K, T):
     """The packed-weight kernel at the (M, K) pairs of the paper-best model -- one and two 32-row blocks per wave, short and
     long contractions, edge / dead column tiles -- against fp64, beside the fp32-MFMA kernel on the same operands; weights
     with rows of very different magnitude (the packer scales per row) and X rows spread over e^+-3 (per-column scales)."""
+    import gemm_matrix
     B = 2
     ldt = (T + 127) // 128 * 128
     X = padded(B, K, T, ldt) * torch.exp(3 * rnd(B, K, 1))
@@ -361,10 +387,17 @@ def test_gemm_packed_weights_model_shapes(M, K, T):
         else:
             kw.update(arith=sepkernels.ARITH_F32)
         HIP.pw_gemm(**kw)
+        # the instance the dispatch tables give this shape (tests/gemm_matrix.py restates them): the producer / consumer kernel from K = 512
+        # or M = 1024 when ldt % 256 == 0 (256 x 128 tiles when M % 256 == 0, else 128 x 256), the cooperative kernel below that
+        case = dict(M=M, K=K, ldt=ldt, pro=0, epi=0, tr=0, k_split=0, m_split=0, arith=kw["arith"], packed=name == "packed")
+        assert sepkernels.last_kernel() == gemm_matrix.dispatch({k: os.environ[k] for k in gemm_matrix.SWITCHES if k in os.environ}, case)
         device_sync()
         assert torch.isfinite(Y).all()
         assert (Y[..., T:] == 0).all()
         err[name] = (((Y.cpu().double() - ref)[..., :T]).abs() / scale).max().item()
+    if not any(k in os.environ for k in gemm_matrix.SWITCHES):
+        assert sepkernels.last_kernel().startswith({(128, 512): "pc<2,2,", (256, 512): "pc<4,1,", (512, 128): "coop<2,", (1024, 128): "pc<4,1,", (128, 1024): "pc<2,2,",
+                                                    (512, 256): "coop<2,"}[(M, K)])
     assert err["f32"] <= 5e-6, err
     assert err["packed"] <= max(3 * err["f32"], 6e-7), err
 

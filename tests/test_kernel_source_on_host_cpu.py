@@ -72,7 +72,7 @@ GEMM_CASES = [
     ("f16x3-packed", "test_gemm_dgrad_prelu_bwd", ()),
     ("f16x3-packed", "test_gemm_dgrad_two_sources_plain", (512, 700)),
     ("f16x3-packed", "test_gemm_packed_heads_residual_accumulate", ()),
-    ("f16x3", "test_gemm_heads_plain_input_residual_accumulate", ()),           # the staged causal layers' heads and heads^T: the direct kernel, fp32 weights
+    ("f16x3", "test_gemm_heads_plain_input_residual_accumulate", ()),           # the staged causal layers' heads and heads^T
     ("f16x3", "test_gemm_dgrad_two_sources_plain", (256, 130)),
     ("f32", "test_gemm_gln_bwd_prologue", (0,)),
     ("bf16x6", "test_wgrad_two_sources_gln_prelu", ()),
@@ -83,25 +83,41 @@ GEMM_CASES = [
     ("f16x3-packed", "test_gemm_gln_bwd_prologue_several_row_tiles", (256, 64)),
     ("f16x3", "test_gemm_gln_bwd_prologue_several_row_tiles", (192, 48)),
     ("f16x3", "test_wgrad_plain", (2, 256, 128, 300, 3)),
-    ("bf16x6", "test_wgrad_sample_aligned_slabs_and_gln_sums_from_them", (2, 256, 128, 300, 3)),      # producer / consumer kernel
+    ("bf16x6", "test_wgrad_sample_aligned_slabs_and_gln_sums_from_them", (2, 256, 128, 300, 3)),
     ("f32", "test_wgrad_sample_aligned_slabs_and_gln_sums_from_them", (3, 32, 20, 500, 2)),
     ("bf16x6", "test_wgrad_plain", (2, 128, 256, 130, 1)),
     ("f32", "test_wgrad_plain", (2, 32, 4, 201, 2)),
-    (None, "test_gemm_packed_weights_model_shapes", (128, 512, 130)),        # producer / consumer kernel, 256-column workgroup tile
-    (None, "test_gemm_packed_weights_model_shapes", (512, 128, 130)),        # cooperative kernel
-    (None, "test_gemm_packed_weights_model_shapes", (1024, 128, 130)),       # producer / consumer kernel, 4 x 1 consumer waves
+    (None, "test_gemm_packed_weights_model_shapes", (128, 512, 130)),
+    (None, "test_gemm_packed_weights_model_shapes", (512, 128, 130)),
+    (None, "test_gemm_packed_weights_model_shapes", (1024, 128, 130)),
+    ("f16x3-packed", "test_gemm_dgrad_prelu_bwd_long_contraction", ()),
+    ("f16x3-packed", "test_gemm_stats_epilogue_long_contraction", ()),
     (None, "test_gemm_packed_adversarial_operands", ("late_jump_k1024",)),
     (None, "test_gemm_prelu_prologues_any_slope", (-0.3,)),
     (None, "test_wgrad_f16_adversarial_operands", ("late_jumps",)),
     (None, "test_wgrad_f16_adversarial_operands", ("zero_rows_then_signal",)),
-    ("f16x3", "test_wgrad_plain", (2, 512, 128, 999, 7)),                      # the scaled two-part fp16 weight-gradient kernel
+    ("f16x3", "test_wgrad_plain", (2, 512, 128, 999, 7)),
     ("f16x3", "test_wgrad_two_sources_gln_prelu", ()),
-    (None, "test_wgrad_with_a_presplit_second_source", (2, 128, 300, 2)),            # sep_split_rows + the G2_pre form of the fp16 weight-gradient kernel
-    ("f16x3", "test_wgrad_batch_equals_separate_calls", (1, 256, 128, 300, 2, 3)),   # the batched grid of the fp16 producer / consumer kernel
-    ("f32", "test_wgrad_batch_equals_separate_calls", (2, 64, 32, 201, 2, 2)),       # ... and the entry point's n-calls fallback
+    (None, "test_wgrad_with_a_presplit_second_source", (2, 128, 300, 2)),            # sep_split_rows + the G2_pre form
+    ("f16x3", "test_wgrad_batch_equals_separate_calls", (1, 256, 128, 300, 2, 3)),
+    ("f32", "test_wgrad_batch_equals_separate_calls", (2, 64, 32, 201, 2, 2)),
     (None, "test_pack_weights_reproduces_the_weights", ()),
     (None, "test_reduce_slabs_and_f64", ()),
 ]
+
+# which kernel instance the LAST sep_pw_gemm / sep_pw_wgrad launch of a row must have gone to (sepkernels.last_kernel()); the model-shape
+# rows and the two long-contraction rows assert theirs inside the test function
+LAST_KERNEL = {
+    ("f16x3", "test_gemm_heads_plain_input_residual_accumulate", ()): "direct<false,SEP_PRO_NONE,false,SEP_EPI_RESIDUAL,arith=2>",      # the direct kernel, fp32 weights
+    ("bf16x6", "test_wgrad_sample_aligned_slabs_and_gln_sums_from_them", (2, 256, 128, 300, 3)): "wgrad_pc<4,1,SEP_PRO_PRELU>",         # producer / consumer kernel
+    ("f32", "test_wgrad_sample_aligned_slabs_and_gln_sums_from_them", (3, 32, 20, 500, 2)): "wgrad_direct<SEP_PRO_PRELU>",
+    ("bf16x6", "test_wgrad_plain", (2, 128, 256, 130, 1)): "wgrad_pc<2,2,SEP_PRO_NONE>",                                                # ... its 128 x 256 tile
+    ("f16x3", "test_wgrad_plain", (2, 512, 128, 999, 7)): "wgrad_pc16<4,1,SEP_PRO_NONE>",                                               # the scaled two-part fp16 weight-gradient kernel
+    ("f16x3", "test_wgrad_two_sources_gln_prelu", ()): "wgrad_split<SEP_PRO_GLN_PRELU>",
+    (None, "test_wgrad_with_a_presplit_second_source", (2, 128, 300, 2)): "wgrad_pc16_pre<4,1,SEP_PRO_PRELU>",                          # the G2_pre form of the fp16 kernel
+    ("f16x3", "test_wgrad_batch_equals_separate_calls", (1, 256, 128, 300, 2, 3)): "wgrad_pc16_batch<4,1,SEP_PRO_NONE>",                # the batched grid of the fp16 producer / consumer kernel
+    ("f32", "test_wgrad_batch_equals_separate_calls", (2, 64, 32, 201, 2, 2)): "wgrad_direct<SEP_PRO_NONE>",                            # ... and the entry point's n-calls fallback
+}
 
 
 @pytest.fixture(scope="module")
@@ -131,14 +147,17 @@ def test_kernel_source_on_the_host_matches_the_restatement(on_host, name, params
 def test_gemm_kernel_source_on_the_host_matches_the_restatement(on_host, arith, name, args):
     import sepkernels
     if arith is None:
-        return getattr(GK, name)(*args)
-    prev = sepkernels.set_gemm_arith(arith.split("-")[0])
-    GK.PACKED[0] = arith.endswith("packed")
-    try:
-        getattr(GK, name)(*args, arith)
-    finally:
-        GK.PACKED[0] = False
-        sepkernels.set_gemm_arith(prev)
+        getattr(GK, name)(*args)
+    else:
+        prev = sepkernels.set_gemm_arith(arith.split("-")[0])
+        GK.PACKED[0] = arith.endswith("packed")
+        try:
+            getattr(GK, name)(*args, arith)
+        finally:
+            GK.PACKED[0] = False
+            sepkernels.set_gemm_arith(prev)
+    if (arith, name, args) in LAST_KERNEL:
+        assert sepkernels.last_kernel() == LAST_KERNEL[(arith, name, args)]
 
 
 @pytest.mark.parametrize("config", ["tiny", "softmax"])
