@@ -11,20 +11,33 @@
 //   sep_online_decoder_fwd    mask * w, synthesis and overlap-add into [tail | n S]: n S final samples, new tail -> tail_next
 //   sep_online_advance        frame counters += n, carry <- carry_next, tail <- tail_next (the last launch of a chunk)
 //   sep_online_reset          zero the state of the streams a device mask selects
+// Every entry point of a chunk has a sibling sep_online_*_sel that takes `const int32_t* slots` (device memory, num_streams distinct entries):
+// the pass then has num_streams column blocks and block j works on the state rows of stream slots[j], so a separator with many slots runs
+// a chunk of the few that have audio.  Both forms are the same kernel templates; without a slot list block j works on stream j.
 // Everything that changes from chunk to chunk (frame counters, running sums, histories, carries, tails) lives in device memory, so a
 // recorded chunk step (sep_run_sequence) replays correctly.  No atomics: every result is formed in a fixed order, replays are bitwise.
 // State that is read and written by the same launch is owned by ONE workgroup that reads before a barrier and writes after it (cLN sums,
 // depthwise histories); the encoder carry and the decoder tail are read by many workgroups and therefore written to a second buffer that
-// sep_online_advance copies back.
+// sep_online_advance copies back.  With a slot list the owner of a stream's state is the workgroup of the column block that names it
+// (entries are distinct), and state rows of streams the list does not name are neither read nor written, the second buffers included.
 #include "common.hpp"
 
 namespace {
 
+// The stream whose state column block j works on.  SEL is a template argument of every kernel below, so the instance behind the plain
+// entry points (SEL = false, slots unused) is the code it was before the slot list existed.
+template <bool SEL>
+__device__ __forceinline__ int slot_of(const int32_t* __restrict__ slots, const int j) {
+    if constexpr (SEL) return slots[j];
+    else return j;
+}
+
 // w[nb][s n + f] = [ReLU] sum_k E[nb][k] ext_s[f S + k], ext_s = [carry_s (L - S) | chunk_s (n S)];  columns [num_streams n, ldt) = 0.
 // carry_next_s = ext_s[n S .. n S + L - S).
+template <bool SEL>
 __global__ __launch_bounds__(256) void online_encoder_kernel(const float* __restrict__ chunk, const float* __restrict__ E, const float* __restrict__ carry,
                                                              float* __restrict__ carry_next, float* __restrict__ w, int num_streams, int L, int S, int n,
-                                                             int ldt, int relu) {
+                                                             int ldt, int relu, const int32_t* __restrict__ slots) {
     const int nb = blockIdx.y;
     const int col = blockIdx.x * 256 + threadIdx.x;
     const int keep = L - S;
@@ -34,7 +47,7 @@ __global__ __launch_bounds__(256) void online_encoder_kernel(const float* __rest
         float acc = 0.f;
         if (col < cols) {
             const int s = col / n, f = col - s * n;
-            const float* cs = carry + (size_t)s * keep;
+            const float* cs = carry + (size_t)slot_of<SEL>(slots, s) * keep;
             const float* xs = chunk + (size_t)s * span;
             const float* e = E + (size_t)nb * L;
             for (int k = 0; k < L; ++k) {
@@ -50,7 +63,8 @@ __global__ __launch_bounds__(256) void online_encoder_kernel(const float* __rest
         for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < (int64_t)num_streams * keep; g += (int64_t)gridDim.x * 256) {
             const int s = (int)(g / keep), i = (int)(g - (int64_t)s * keep);
             const int64_t e = span + i;                                   // index into ext_s
-            carry_next[g] = e < keep ? carry[(size_t)s * keep + e] : chunk[(size_t)s * span + (e - keep)];
+            const size_t st = (size_t)slot_of<SEL>(slots, s) * keep;
+            carry_next[st + i] = e < keep ? carry[st + e] : chunk[(size_t)s * span + (e - keep)];
         }
     }
 }
@@ -61,9 +75,11 @@ constexpr int OC_CG = 8;          // channel groups: 8 x 32 = 256 threads
 // One workgroup per stream: tiles of 32 frames, column sums over the channels (fp32 per channel group -> fp64), an inclusive fp64 scan
 // over the tile on top of the running sums of everything the stream has seen, then the apply pass over the tile.  count = C (t + 1) with t
 // the absolute frame index (frames[s] + f).  The running sums are read by wave 0 at the start and written by lane 0 after the last barrier.
+template <bool SEL>
 __global__ __launch_bounds__(256) void online_cln_kernel(const float* __restrict__ x, const float* __restrict__ alpha, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float* __restrict__ y, double* __restrict__ sums, int sums_stride,
-                                                         const int64_t* __restrict__ frames, int C, int n, int ldt, float eps) {
+                                                         const int64_t* __restrict__ frames, int C, int n, int ldt, float eps,
+                                                         const int32_t* __restrict__ slots) {
     __shared__ float red[2][OC_CG][OC_TW];
     __shared__ float mr[2][OC_TW];
     const int s = blockIdx.x, tid = threadIdx.x;
@@ -71,12 +87,13 @@ __global__ __launch_bounds__(256) void online_cln_kernel(const float* __restrict
     const bool act = alpha != nullptr;
     const float al = act ? alpha[0] : 1.f;
     const size_t col0 = (size_t)s * n;
-    double* sm = sums + (size_t)s * sums_stride;
+    const int st = slot_of<SEL>(slots, s);
+    double* sm = sums + (size_t)st * sums_stride;
     double ca = 0.0, cq = 0.0, t0 = 0.0;
     if (tid < 64) {
         ca = sm[0];
         cq = sm[1];
-        t0 = (double)frames[s];
+        t0 = (double)frames[st];
     }
     for (int f0 = 0; f0 < n; f0 += OC_TW) {
         const int f = f0 + fl;
@@ -148,12 +165,14 @@ __global__ __launch_bounds__(256) void online_cln_kernel(const float* __restrict
 // One workgroup per (channel, stream) row: the history is copied to LDS before the barrier, outputs and the new history are formed after
 // it from the LDS copy and the (unmodified) input, so a chunk shorter than the history (n < (P - 1) d) cannot race with itself.
 // y[f] = bias + sum_k w[k] ext[f + k d], ext = [history ((P - 1) d) | x (n)];  new history = ext[n .. n + (P - 1) d).
+template <bool SEL>
 __global__ __launch_bounds__(256) void online_depthwise_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                               float* __restrict__ ring, int64_t ring_stride, float* __restrict__ y, int n, int ldt, int P, int d) {
+                                                               float* __restrict__ ring, int64_t ring_stride, float* __restrict__ y, int n, int ldt, int P, int d,
+                                                               const int32_t* __restrict__ slots) {
     extern __shared__ float hist[];
     const int c = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
     const int D = (P - 1) * d;
-    float* rg = ring + (size_t)s * ring_stride + (size_t)c * D;
+    float* rg = ring + (size_t)slot_of<SEL>(slots, s) * ring_stride + (size_t)c * D;
     const float* xr = x + (size_t)c * ldt + (size_t)s * n;
     float* yr = y + (size_t)c * ldt + (size_t)s * n;
     for (int i = tid; i < D; i += 256) hist[i] = rg[i];
@@ -178,16 +197,18 @@ __global__ __launch_bounds__(256) void online_depthwise_kernel(const float* __re
 
 // Thread per output sample i of [0, n S + L - S) of (stream, source): the old tail plus the overlap-add of the frames that cover i
 // (f S <= i < f S + L), latent = w * mask.  i < n S goes to out, the rest to tail_next.
+template <bool SEL>
 __global__ __launch_bounds__(256) void online_decoder_kernel(const float* __restrict__ w, const float* __restrict__ mask, const float* __restrict__ Dm,
                                                              const float* __restrict__ tail, float* __restrict__ tail_next, float* __restrict__ out,
-                                                             int n_src, int N, int L, int S, int n, int ldt) {
+                                                             int n_src, int N, int L, int S, int n, int ldt, const int32_t* __restrict__ slots) {
     const int src = blockIdx.y, s = blockIdx.z;
     const int keep = L - S;
     const int span = n * S;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= span + keep) return;
     const size_t row = (size_t)s * n_src + src;
-    float acc = i < keep ? tail[row * keep + i] : 0.f;
+    const size_t trow = (size_t)slot_of<SEL>(slots, s) * n_src + src;           // the stream's row of tail / tail_next
+    float acc = i < keep ? tail[trow * keep + i] : 0.f;
     const int f_hi = (i / S) < n - 1 ? (i / S) : n - 1;
     const int f_lo = i - L + 1 > 0 ? (i - L + S) / S : 0;
     for (int f = f_lo; f <= f_hi; ++f) {
@@ -199,12 +220,28 @@ __global__ __launch_bounds__(256) void online_decoder_kernel(const float* __rest
         }
     }
     if (i < span) out[row * span + i] = acc;
-    else tail_next[row * keep + (i - span)] = acc;
+    else tail_next[trow * keep + (i - span)] = acc;
 }
 
+template <bool SEL>
 __global__ __launch_bounds__(256) void online_advance_kernel(int64_t* __restrict__ frames, float* __restrict__ carry, const float* __restrict__ carry_next,
                                                              int64_t carry_total, float* __restrict__ tail, const float* __restrict__ tail_next,
-                                                             int64_t tail_total, int num_streams, int n) {
+                                                             int64_t tail_total, int num_streams, int n, int carry_len, int tail_len,
+                                                             const int32_t* __restrict__ slots) {
+    if constexpr (SEL) {                                                  // element g of column block g / len -> the same element of its stream's row
+        for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < carry_total || g < tail_total || g < num_streams; g += (int64_t)gridDim.x * 256) {
+            if (g < num_streams) frames[slots[g]] += n;
+            if (g < carry_total) {
+                const int64_t j = g / carry_len, e = (int64_t)slots[j] * carry_len + (g - j * carry_len);
+                carry[e] = carry_next[e];
+            }
+            if (g < tail_total) {
+                const int64_t j = g / tail_len, e = (int64_t)slots[j] * tail_len + (g - j * tail_len);
+                tail[e] = tail_next[e];
+            }
+        }
+        return;
+    }
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < carry_total || g < tail_total || g < num_streams; g += (int64_t)gridDim.x * 256) {
         if (g < num_streams) frames[g] += n;
         if (g < carry_total) carry[g] = carry_next[g];
@@ -230,68 +267,130 @@ inline int ceil_div_i(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 }  // namespace
 
-extern "C" int sep_online_encoder_fwd(const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N,
-                                      int L, int S, int n, int ldt, int relu, sep_stream_t stream) {
-    SEP_REQUIRE(chunk && E && w && num_streams > 0 && N > 0 && S > 0 && L >= S && L % S == 0 && n > 0, "sep_online_encoder_fwd: bad arguments");
-    SEP_REQUIRE((carry && carry_next) || L == S, "sep_online_encoder_fwd: carry buffers missing");
-    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0 && N <= 65535, "sep_online_encoder_fwd: bad sizes (streams=%d n=%d ldt=%d N=%d)",
-                num_streams, n, ldt, N);
-    hipLaunchKernelGGL(online_encoder_kernel, dim3(ceil_div_i(ldt, 256), N), dim3(256), 0, (hipStream_t)stream, chunk, E, carry, carry_next, w,
-                       num_streams, L, S, n, ldt, relu);
-    SEP_CHECK_LAUNCH("sep_online_encoder_fwd");
+// The launchers behind both forms of an entry point: `who` names the caller in its errors, slots == nullptr is the plain form.
+static int online_encoder(const char* who, const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N,
+                          int L, int S, int n, int ldt, int relu, const int32_t* slots, sep_stream_t stream) {
+    SEP_REQUIRE(chunk && E && w && num_streams > 0 && N > 0 && S > 0 && L >= S && L % S == 0 && n > 0, "%s: bad arguments", who);
+    SEP_REQUIRE((carry && carry_next) || L == S, "%s: carry buffers missing", who);
+    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0 && N <= 65535, "%s: bad sizes (streams=%d n=%d ldt=%d N=%d)", who, num_streams, n, ldt,
+                N);
+    const auto kern = slots ? online_encoder_kernel<true> : online_encoder_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(ceil_div_i(ldt, 256), N), dim3(256), 0, (hipStream_t)stream, chunk, E, carry, carry_next, w,
+                       num_streams, L, S, n, ldt, relu, slots);
+    SEP_CHECK_LAUNCH(who);
     return 0;
 }
 
-extern "C" int sep_online_cln_fwd(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums, int sums_stride,
-                                  const int64_t* frames, int num_streams, int C, int n, int ldt, float eps, sep_stream_t stream) {
-    SEP_REQUIRE(x && gamma && beta && y && sums && frames && num_streams > 0 && C > 0 && n > 0 && sums_stride >= 2, "sep_online_cln_fwd: bad arguments");
-    SEP_REQUIRE(x != y, "sep_online_cln_fwd: y may not alias x");
-    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0, "sep_online_cln_fwd: bad sizes (streams=%d n=%d ldt=%d)", num_streams, n, ldt);
-    hipLaunchKernelGGL(online_cln_kernel, dim3(num_streams), dim3(256), 0, (hipStream_t)stream, x, alpha, gamma, beta, y, sums, sums_stride, frames,
-                       C, n, ldt, eps);
-    SEP_CHECK_LAUNCH("sep_online_cln_fwd");
+static int online_cln(const char* who, const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums, int sums_stride,
+                      const int64_t* frames, int num_streams, int C, int n, int ldt, float eps, const int32_t* slots, sep_stream_t stream) {
+    SEP_REQUIRE(x && gamma && beta && y && sums && frames && num_streams > 0 && C > 0 && n > 0 && sums_stride >= 2, "%s: bad arguments", who);
+    SEP_REQUIRE(x != y, "%s: y may not alias x", who);
+    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0, "%s: bad sizes (streams=%d n=%d ldt=%d)", who, num_streams, n, ldt);
+    const auto kern = slots ? online_cln_kernel<true> : online_cln_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(num_streams), dim3(256), 0, (hipStream_t)stream, x, alpha, gamma, beta, y, sums, sums_stride, frames,
+                       C, n, ldt, eps, slots);
+    SEP_CHECK_LAUNCH(who);
     return 0;
 }
 
-extern "C" int sep_online_depthwise_fwd(const float* x, const float* w, const float* bias, float* ring, int64_t ring_stride, float* y, int num_streams,
-                                        int C, int n, int ldt, int P, int dilation, sep_stream_t stream) {
+static int online_depthwise(const char* who, const float* x, const float* w, const float* bias, float* ring, int64_t ring_stride, float* y,
+                            int num_streams, int C, int n, int ldt, int P, int dilation, const int32_t* slots, sep_stream_t stream) {
     SEP_REQUIRE(x && w && ring && y && x != y && num_streams > 0 && num_streams <= 65535 && C > 0 && n > 0 && P >= 2 && dilation > 0,
-                "sep_online_depthwise_fwd: bad arguments");
+                "%s: bad arguments", who);
     const int64_t D = (int64_t)(P - 1) * dilation;
-    SEP_REQUIRE(D <= 16384, "sep_online_depthwise_fwd: history of %lld frames exceeds LDS", (long long)D);
-    SEP_REQUIRE(ring_stride >= (int64_t)C * D, "sep_online_depthwise_fwd: ring_stride %lld < C (P - 1) d", (long long)ring_stride);
-    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0, "sep_online_depthwise_fwd: bad sizes (streams=%d n=%d ldt=%d)", num_streams, n, ldt);
-    hipLaunchKernelGGL(online_depthwise_kernel, dim3(C, num_streams), dim3(256), (size_t)D * sizeof(float), (hipStream_t)stream, x, w, bias, ring,
-                       ring_stride, y, n, ldt, P, dilation);
-    SEP_CHECK_LAUNCH("sep_online_depthwise_fwd");
+    SEP_REQUIRE(D <= 16384, "%s: history of %lld frames exceeds LDS", who, (long long)D);
+    SEP_REQUIRE(ring_stride >= (int64_t)C * D, "%s: ring_stride %lld < C (P - 1) d", who, (long long)ring_stride);
+    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0, "%s: bad sizes (streams=%d n=%d ldt=%d)", who, num_streams, n, ldt);
+    const auto kern = slots ? online_depthwise_kernel<true> : online_depthwise_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(C, num_streams), dim3(256), (size_t)D * sizeof(float), (hipStream_t)stream, x, w, bias, ring,
+                       ring_stride, y, n, ldt, P, dilation, slots);
+    SEP_CHECK_LAUNCH(who);
     return 0;
 }
 
-extern "C" int sep_online_decoder_fwd(const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out, int num_streams,
-                                      int n_src, int N, int L, int S, int n, int ldt, sep_stream_t stream) {
+static int online_decoder(const char* who, const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out,
+                          int num_streams, int n_src, int N, int L, int S, int n, int ldt, const int32_t* slots, sep_stream_t stream) {
     SEP_REQUIRE(w && mask && D && out && num_streams > 0 && num_streams <= 65535 && n_src > 0 && n_src <= 65535 && N > 0 && S > 0 && L >= S &&
-                L % S == 0 && n > 0, "sep_online_decoder_fwd: bad arguments");
-    SEP_REQUIRE((tail && tail_next) || L == S, "sep_online_decoder_fwd: tail buffers missing");
-    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0, "sep_online_decoder_fwd: bad sizes (streams=%d n=%d ldt=%d)", num_streams, n, ldt);
-    hipLaunchKernelGGL(online_decoder_kernel, dim3(ceil_div_i((int64_t)n * S + L - S, 256), n_src, num_streams), dim3(256), 0, (hipStream_t)stream, w, mask,
-                       D, tail, tail_next, out, n_src, N, L, S, n, ldt);
-    SEP_CHECK_LAUNCH("sep_online_decoder_fwd");
+                L % S == 0 && n > 0, "%s: bad arguments", who);
+    SEP_REQUIRE((tail && tail_next) || L == S, "%s: tail buffers missing", who);
+    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0, "%s: bad sizes (streams=%d n=%d ldt=%d)", who, num_streams, n, ldt);
+    const auto kern = slots ? online_decoder_kernel<true> : online_decoder_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(ceil_div_i((int64_t)n * S + L - S, 256), n_src, num_streams), dim3(256), 0, (hipStream_t)stream, w, mask,
+                       D, tail, tail_next, out, n_src, N, L, S, n, ldt, slots);
+    SEP_CHECK_LAUNCH(who);
     return 0;
 }
 
-extern "C" int sep_online_advance(int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next,
-                                  int tail_len, int num_streams, int n, sep_stream_t stream) {
-    SEP_REQUIRE(frames && num_streams > 0 && n > 0 && carry_len >= 0 && tail_len >= 0, "sep_online_advance: bad arguments");
-    SEP_REQUIRE((carry && carry_next) || carry_len == 0, "sep_online_advance: carry buffers missing");
-    SEP_REQUIRE((tail && tail_next) || tail_len == 0, "sep_online_advance: tail buffers missing");
+static int online_advance(const char* who, int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next,
+                          int tail_len, int num_streams, int n, const int32_t* slots, sep_stream_t stream) {
+    SEP_REQUIRE(frames && num_streams > 0 && n > 0 && carry_len >= 0 && tail_len >= 0, "%s: bad arguments", who);
+    SEP_REQUIRE((carry && carry_next) || carry_len == 0, "%s: carry buffers missing", who);
+    SEP_REQUIRE((tail && tail_next) || tail_len == 0, "%s: tail buffers missing", who);
     const int64_t ct = (int64_t)num_streams * carry_len, tt = (int64_t)num_streams * tail_len;
     int64_t most = ct > tt ? ct : tt;
     most = most > num_streams ? most : num_streams;
     const int grid = ceil_div_i(most, 256) > 1024 ? 1024 : ceil_div_i(most, 256);
-    hipLaunchKernelGGL(online_advance_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, carry, carry_next, ct, tail, tail_next, tt,
-                       num_streams, n);
-    SEP_CHECK_LAUNCH("sep_online_advance");
+    const auto kern = slots ? online_advance_kernel<true> : online_advance_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, carry, carry_next, ct, tail, tail_next, tt,
+                       num_streams, n, carry_len, tail_len, slots);
+    SEP_CHECK_LAUNCH(who);
     return 0;
+}
+
+extern "C" int sep_online_encoder_fwd(const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N,
+                                      int L, int S, int n, int ldt, int relu, sep_stream_t stream) {
+    return online_encoder("sep_online_encoder_fwd", chunk, E, carry, carry_next, w, num_streams, N, L, S, n, ldt, relu, nullptr, stream);
+}
+
+extern "C" int sep_online_encoder_fwd_sel(const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N,
+                                          int L, int S, int n, int ldt, int relu, const int32_t* slots, sep_stream_t stream) {
+    SEP_REQUIRE(slots, "sep_online_encoder_fwd_sel: slots missing");
+    return online_encoder("sep_online_encoder_fwd_sel", chunk, E, carry, carry_next, w, num_streams, N, L, S, n, ldt, relu, slots, stream);
+}
+
+extern "C" int sep_online_cln_fwd(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums, int sums_stride,
+                                  const int64_t* frames, int num_streams, int C, int n, int ldt, float eps, sep_stream_t stream) {
+    return online_cln("sep_online_cln_fwd", x, alpha, gamma, beta, y, sums, sums_stride, frames, num_streams, C, n, ldt, eps, nullptr, stream);
+}
+
+extern "C" int sep_online_cln_fwd_sel(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums,
+                                      int sums_stride, const int64_t* frames, int num_streams, int C, int n, int ldt, float eps, const int32_t* slots,
+                                      sep_stream_t stream) {
+    SEP_REQUIRE(slots, "sep_online_cln_fwd_sel: slots missing");
+    return online_cln("sep_online_cln_fwd_sel", x, alpha, gamma, beta, y, sums, sums_stride, frames, num_streams, C, n, ldt, eps, slots, stream);
+}
+
+extern "C" int sep_online_depthwise_fwd(const float* x, const float* w, const float* bias, float* ring, int64_t ring_stride, float* y, int num_streams,
+                                        int C, int n, int ldt, int P, int dilation, sep_stream_t stream) {
+    return online_depthwise("sep_online_depthwise_fwd", x, w, bias, ring, ring_stride, y, num_streams, C, n, ldt, P, dilation, nullptr, stream);
+}
+
+extern "C" int sep_online_depthwise_fwd_sel(const float* x, const float* w, const float* bias, float* ring, int64_t ring_stride, float* y,
+                                            int num_streams, int C, int n, int ldt, int P, int dilation, const int32_t* slots, sep_stream_t stream) {
+    SEP_REQUIRE(slots, "sep_online_depthwise_fwd_sel: slots missing");
+    return online_depthwise("sep_online_depthwise_fwd_sel", x, w, bias, ring, ring_stride, y, num_streams, C, n, ldt, P, dilation, slots, stream);
+}
+
+extern "C" int sep_online_decoder_fwd(const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out, int num_streams,
+                                      int n_src, int N, int L, int S, int n, int ldt, sep_stream_t stream) {
+    return online_decoder("sep_online_decoder_fwd", w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n, ldt, nullptr, stream);
+}
+
+extern "C" int sep_online_decoder_fwd_sel(const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out,
+                                          int num_streams, int n_src, int N, int L, int S, int n, int ldt, const int32_t* slots, sep_stream_t stream) {
+    SEP_REQUIRE(slots, "sep_online_decoder_fwd_sel: slots missing");
+    return online_decoder("sep_online_decoder_fwd_sel", w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n, ldt, slots, stream);
+}
+
+extern "C" int sep_online_advance(int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next,
+                                  int tail_len, int num_streams, int n, sep_stream_t stream) {
+    return online_advance("sep_online_advance", frames, carry, carry_next, carry_len, tail, tail_next, tail_len, num_streams, n, nullptr, stream);
+}
+
+extern "C" int sep_online_advance_sel(int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next,
+                                      int tail_len, int num_streams, int n, const int32_t* slots, sep_stream_t stream) {
+    SEP_REQUIRE(slots, "sep_online_advance_sel: slots missing");
+    return online_advance("sep_online_advance_sel", frames, carry, carry_next, carry_len, tail, tail_next, tail_len, num_streams, n, slots, stream);
 }
 
 extern "C" int sep_online_reset(const uint8_t* mask, int num_streams, int64_t* frames, float* carry, int carry_len, double* sums, int sums_len,

@@ -63,6 +63,8 @@ const seq_entry SEQ_TABLE[] = {
     SEQ_FN(sep_chunk_to_tokens), SEQ_FN(sep_tokens_to_chunk), SEQ_FN(sep_memset), SEQ_FN(sep_absmax), SEQ_FN(sep_pit_finish), SEQ_FN(sep_axpby), SEQ_FN(sep_split_rows),
     SEQ_FN(sep_online_encoder_fwd), SEQ_FN(sep_online_cln_fwd), SEQ_FN(sep_online_depthwise_fwd), SEQ_FN(sep_online_decoder_fwd),
     SEQ_FN(sep_online_advance), SEQ_FN(sep_online_reset),
+    SEQ_FN(sep_online_encoder_fwd_sel), SEQ_FN(sep_online_cln_fwd_sel), SEQ_FN(sep_online_depthwise_fwd_sel), SEQ_FN(sep_online_decoder_fwd_sel),
+    SEQ_FN(sep_online_advance_sel),
     SEQ_FN(sep_cln_stats), SEQ_FN(sep_depthwise_cln_fwd), SEQ_FN(sep_depthwise_cln_bwd_weight), SEQ_FN(sep_sum_f64),
 };
 constexpr int SEQ_COUNT = (int)(sizeof(SEQ_TABLE) / sizeof(SEQ_TABLE[0]));

@@ -452,15 +452,20 @@ class ConvTasNet(nn.Module):
             return est, latent[..., :F_]
         return out, None
 
-    def online_separator(self, num_streams=1, chunk_size=None, record=True):
+    def online_separator(self, num_streams=1, chunk_size=None, record=True, max_recordings=8):
         """A sepkernels.online.OnlineSeparator: chunk-by-chunk separation of `num_streams` mono streams by this CAUSAL model, with an algorithmic
         delay of L - S samples.  Chunks are (num_streams, 1, k * stride) on the model's device; each returns (num_streams, n_sources, k * stride);
         flush() returns the last L - S samples and resets.  Concatenated, the outputs equal model(F.pad(x, (L - S, 0))) for an input x whose
         length is a multiple of the stride.  The first chunk of `chunk_size` samples (default: the first chunk's size) is recorded and replayed
         by one sep_run_sequence call afterwards (record=False: every chunk is launched eagerly).  Refuses non-causal models (ValueError: gLN
-        needs the whole signal), causal models outside the staged family (NotImplementedError with `staged_reason`) and in_channels != 1."""
+        needs the whole signal), causal models outside the staged family (NotImplementedError with `staged_reason`) and in_channels != 1.
+        The streams keep their own clocks: sep(chunk, streams=[...]) takes (A, 1, k * stride) for the A streams it names (indices in any order,
+        an integer tensor or a bool mask) and advances only those, at the cost of A streams; flush(streams) returns and resets only those; so
+        the equality above holds for every stream by itself, whichever others took part in which calls.  Duplicate or out-of-range indices, an
+        empty selection, a mask of the wrong length and a chunk whose rows do not match the selection are ValueErrors.  Subset steps at
+        `chunk_size` are recorded per number of selected streams; `max_recordings` (default 8) of them are kept, least recently used out first."""
         from sepkernels.online import OnlineSeparator
-        return OnlineSeparator(self, num_streams=num_streams, chunk_size=chunk_size, record=record)
+        return OnlineSeparator(self, num_streams=num_streams, chunk_size=chunk_size, record=record, max_recordings=max_recordings)
 
     def _run_composed(self, mixture, want_latent):
         """The reference's own sequence (conv_tasnet.py:121-171) on this repository's modules, for configurations outside

@@ -204,6 +204,12 @@ SIGNATURES = {
     "sep_online_decoder_fwd": [_vp] * 6 + [_I] * 7 + [_vp],
     "sep_online_advance": [_vp] * 3 + [_I] + [_vp] * 2 + [_I] * 3 + [_vp],
     "sep_online_reset": [_vp, _I, _vp, _vp, _I, _vp, _I, _vp, _L, _vp, _I, _vp],
+    # ... the same five with a device slot list (const int32_t* slots) in front of the stream: column block j works on stream slots[j]
+    "sep_online_encoder_fwd_sel": [_vp] * 5 + [_I] * 7 + [_vp, _vp],
+    "sep_online_cln_fwd_sel": [_vp] * 6 + [_I, _vp] + [_I] * 4 + [_F, _vp, _vp],
+    "sep_online_depthwise_fwd_sel": [_vp] * 4 + [_L, _vp] + [_I] * 6 + [_vp, _vp],
+    "sep_online_decoder_fwd_sel": [_vp] * 6 + [_I] * 7 + [_vp, _vp],
+    "sep_online_advance_sel": [_vp] * 3 + [_I] + [_vp] * 2 + [_I] * 3 + [_vp, _vp],
     # the causal layer's first norm folded into its depthwise kernels (ABI 23, additive): csrc/causal.hip, sepkernels/causal.py
     "sep_cln_stats": [_vp] * 4 + [_I] * 4 + [_F, _vp, _vp],
     "sep_depthwise_cln_fwd": [_vp] * 9 + [_I] * 7 + [_vp],
@@ -779,6 +785,32 @@ class HipBackend:
     def online_reset(self, mask, num_streams, frames, carry, carry_len, sums, sums_len, rings, rings_len, tail, tail_len):
         _check(load().sep_online_reset(_ptr(mask, torch.uint8), num_streams, _ptr(frames, torch.int64), _ptr(carry, _f32), carry_len, _ptr(sums, _f64),
                                        sums_len, _ptr(rings, _f32), rings_len, _ptr(tail, _f32), tail_len, _stream()), "sep_online_reset")
+
+    # ... on a selection of the streams: `slots` (int32, num_streams entries on the device) names the stream of every column block
+    def online_encoder_fwd_sel(self, chunk, E, carry, carry_next, w, num_streams, N, L, S, n, ldt, relu, slots):
+        _check(load().sep_online_encoder_fwd_sel(_ptr(chunk, _f32), _ptr(E, _f32), _ptr(carry, _f32), _ptr(carry_next, _f32), _ptr(w, _f32),
+                                                 num_streams, N, L, S, n, ldt, int(relu), _ptr(slots, torch.int32), _stream()),
+               "sep_online_encoder_fwd_sel")
+
+    def online_cln_fwd_sel(self, x, alpha, gamma, beta, y, sums, sums_stride, frames, num_streams, C, n, ldt, eps, slots):
+        _check(load().sep_online_cln_fwd_sel(_ptr(x, _f32), _ptr(alpha, _f32), _ptr(gamma, _f32), _ptr(beta, _f32), _ptr(y, _f32), _ptr(sums, _f64),
+                                             sums_stride, _ptr(frames, torch.int64), num_streams, C, n, ldt, eps, _ptr(slots, torch.int32), _stream()),
+               "sep_online_cln_fwd_sel")
+
+    def online_depthwise_fwd_sel(self, x, w, bias, ring, ring_stride, y, num_streams, C, n, ldt, P, dilation, slots):
+        _check(load().sep_online_depthwise_fwd_sel(_ptr(x, _f32), _ptr(w, _f32), _ptr(bias, _f32), _ptr(ring, _f32), ring_stride, _ptr(y, _f32),
+                                                   num_streams, C, n, ldt, P, dilation, _ptr(slots, torch.int32), _stream()),
+               "sep_online_depthwise_fwd_sel")
+
+    def online_decoder_fwd_sel(self, w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n, ldt, slots):
+        _check(load().sep_online_decoder_fwd_sel(_ptr(w, _f32), _ptr(mask, _f32), _ptr(D, _f32), _ptr(tail, _f32), _ptr(tail_next, _f32),
+                                                 _ptr(out, _f32), num_streams, n_src, N, L, S, n, ldt, _ptr(slots, torch.int32), _stream()),
+               "sep_online_decoder_fwd_sel")
+
+    def online_advance_sel(self, frames, carry, carry_next, carry_len, tail, tail_next, tail_len, num_streams, n, slots):
+        _check(load().sep_online_advance_sel(_ptr(frames, torch.int64), _ptr(carry, _f32), _ptr(carry_next, _f32), carry_len, _ptr(tail, _f32),
+                                             _ptr(tail_next, _f32), tail_len, num_streams, n, _ptr(slots, torch.int32), _stream()),
+               "sep_online_advance_sel")
 
 
 _backend = HipBackend()

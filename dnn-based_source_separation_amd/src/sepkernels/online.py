@@ -21,7 +21,28 @@ streams; the state that carries from chunk to chunk (encoder carry, frame counte
 overlap-add tail) lives in device memory and is read by the kernels of csrc/online.hip.  The first chunk of `chunk_size` samples is recorded
 (sepkernels.recording) and later chunks of that size replay it with one sep_run_sequence call; other sizes run the same launches eagerly on
 workspaces cached per size.  No gradients: training is out of scope.
+
+Streams on their own clocks.  A separator is a set of `num_streams` SLOTS; sep(chunk, streams=...) advances only the slots it names and
+flush(streams) / reset(streams) end / restart only those, so the contract above holds PER STREAM whichever other streams took part in which
+calls and however long a stream sat idle:
+
+    y = sep(chunk, streams=[7, 2])       # chunk (2, 1, k S): row 0 is slot 7's audio, row 1 slot 2's -> (2, n_sources, k S), same order
+    tail = sep.flush([7])                # (1, n_sources, L - S); slot 7 starts over, every other slot is untouched
+
+    torch.cat(pieces slot s received + [sep.flush([s])], -1) == model(F.pad(x_s, (L - S, 0)))
+
+`streams` is a list of indices in any order, an integer tensor, or a bool mask of num_streams entries (selects in ascending order); duplicates,
+indices out of range, an empty selection and a chunk whose rows do not match the selection are ValueErrors.  All streams of one call share one
+chunk length.  The pass of a subset call runs over the A selected streams only -- A n stream-major columns, T = A n in every product, A
+workgroups (or rows of workgroups) in the state kernels, the sep_online_*_sel entry points -- so idle slots cost their memory and nothing
+else.  The slot list lives in a device buffer of the workspace that is filled before every call like the chunk, so a step recorded for (A, n)
+replays for ANY selection of A slots.  One workspace per chunk length serves every A: its matrices are laid out with the leading dimension
+round_up(A n, 128) inside storage sized for all slots, and a recording per A holds a launch list only.  At most `max_recordings` (default 8)
+of them are kept, the least recently used one is dropped first -- a recording owns no device memory of its own, so dropping one is safe at
+any time and the next call of that A records again.  streams=None is the all-streams call: it issues exactly the launches it always did.
 """
+import collections
+
 import torch
 
 import sepkernels
@@ -52,15 +73,47 @@ class _Workspace:
         self.amax = torch.zeros(1, **f)
 
 
+class _Views:
+    """what _step takes as a workspace: the matrices of one pass over `blocks` column blocks of n frames"""
+
+
+class _SubsetWorkspace:
+    """the activations of the subset calls of one chunk size: storage for all slots, handed out as (C, ldt_A) matrices with
+    ldt_A = round_up(A n, 128) for a call over A of them (every kernel of the pass that writes a matrix zeroes its columns [A n, ldt_A))"""
+
+    def __init__(self, sep, n):
+        f = dict(device=sep.device, dtype=sep.dtype)
+        Bs = sep.num_streams
+        self.n = n
+        self.ldt = ldt = _round_up(Bs * n, 128)
+        self.chunk = torch.zeros(Bs, n * sep.S, **f)
+        self.out = torch.zeros(Bs, sep.n_src, n * sep.S, **f)
+        self.slots = torch.zeros(Bs, device=sep.device, dtype=torch.int32)
+        self.amax = torch.zeros(1, **f)
+        self.rows = dict(w=sep.N, wn=sep.N, xa=sep.Bn, xb=sep.Bn, ha=sep.H, hb=sep.H, total=sep.Sc, m=sep.n_src * sep.N)
+        self.store = {k: torch.zeros(C * ldt, **f) for k, C in self.rows.items()}
+
+    def views(self, A):
+        v = _Views()
+        v.n, v.ldt = self.n, _round_up(A * self.n, 128)
+        for k, C in self.rows.items():
+            setattr(v, k, self.store[k][:C * v.ldt].view(C, v.ldt))
+        v.chunk, v.out, v.amax = self.chunk[:A], self.out[:A], self.amax
+        return v
+
+
 class OnlineSeparator:
     """Chunk-by-chunk separation of `num_streams` independent mono streams by a causal Conv-TasNet (see the module docstring for the contract).
     Built by ConvTasNet.online_separator; reads the model's live parameters at every chunk (an in-place update or load_state_dict is seen at
     the next chunk; after model.to() moved the flat parameter buffer the recording is dropped and made again).
 
     delay        L - S: output sample t + delay is the separated version of input sample t
-    state_bytes  device memory of the per-stream state (carry, frame counter, cLN sums, depthwise histories, overlap-add tail)"""
+    state_bytes  device memory of the per-stream state (carry, frame counter, cLN sums, depthwise histories, overlap-add tail)
 
-    def __init__(self, model, num_streams=1, chunk_size=None, record=True):
+    max_recordings  how many recorded subset steps (one per number of selected streams A, at `chunk_size`) are kept; the least recently used
+                    one is dropped first and recorded again when that A comes back"""
+
+    def __init__(self, model, num_streams=1, chunk_size=None, record=True, max_recordings=8):
         if not model.causal:
             raise ValueError("online separation needs a causal model: gLN (causal=False) normalises over the whole signal, which has not arrived yet")
         if not model.staged:
@@ -69,6 +122,8 @@ class OnlineSeparator:
             raise NotImplementedError("online separation takes mono streams (in_channels=1), the model has in_channels={}".format(model.in_channels))
         if num_streams < 1:
             raise ValueError("num_streams must be >= 1")
+        if max_recordings < 1:
+            raise ValueError("max_recordings must be >= 1")
         K = backend()
         flat = model.flat_parameters()
         if flat is None:
@@ -106,9 +161,17 @@ class OnlineSeparator:
                                                                        self.tail_next))
         self._ws = {}
         self._seq = self._seq_n = self._seq_flat = None
+        self.max_recordings = int(max_recordings)
+        self._sub_ws = {}                                      # chunk frames n -> _SubsetWorkspace
+        self._sub_seqs = collections.OrderedDict()             # A -> Sequence of a subset step at chunk_size, least recently used first
+        self._sub_flat = None
 
     # ------------------------------------------------------------------ public
-    def __call__(self, chunk):
+    def __call__(self, chunk, streams=None):
+        """chunk (num_streams, 1, k S) -> (num_streams, n_sources, k S); with `streams` (indices in any order, an integer tensor or a bool mask)
+        chunk is (A, 1, k S) for the A selected streams in that order, only they advance, and the result is (A, n_sources, k S)"""
+        if streams is not None:
+            return self._call_subset(chunk, self._select(streams))
         n = self._check_chunk(chunk)
         with torch.no_grad():
             ws = self._ws.get(n)
@@ -133,8 +196,15 @@ class OnlineSeparator:
                 self._step(ws, n)
             return ws.out.clone()
 
-    def flush(self):
-        """the last L - S samples of every stream (num_streams, n_sources, L - S); then every stream is reset"""
+    def flush(self, streams=None):
+        """the last L - S samples of every stream (num_streams, n_sources, L - S); then every stream is reset.  With `streams`: of the selected
+        streams in the order given, (A, n_sources, L - S), and only they are reset"""
+        if streams is not None:
+            idx = self._select(streams)
+            with torch.no_grad():
+                out = self.tail.index_select(0, torch.tensor(idx, dtype=torch.int64).to(self.device))
+            self.reset(idx)
+            return out
         with torch.no_grad():
             out = self.tail.clone()
         self.reset()
@@ -161,9 +231,60 @@ class OnlineSeparator:
             backend().online_reset(mask, Bs, self.frames, self.carry if keep else None, keep, self.sums, 2 * self.n_norms,
                                    self.rings if self.ring_len else None, self.ring_len, self.tail if keep else None, self.n_src * keep)
 
+    # ------------------------------------------------------------------ a call on a selection of the streams
+    def _select(self, streams):
+        """-> the selected stream indices in call order, checked: the kernels take the list as it is"""
+        Bs = self.num_streams
+        if torch.is_tensor(streams) and streams.dtype == torch.bool:
+            if streams.numel() != Bs:
+                raise ValueError("the stream mask has {} entries, the separator has {} streams".format(streams.numel(), Bs))
+            idx = torch.nonzero(streams.reshape(-1)).reshape(-1).tolist()
+        else:
+            idx = [int(i) for i in (streams.reshape(-1).tolist() if torch.is_tensor(streams) else streams)]
+        if not idx:
+            raise ValueError("the selection of streams is empty")
+        if any(i < 0 or i >= Bs for i in idx):
+            raise ValueError("stream index out of range 0 .. {}".format(Bs - 1))
+        if len(set(idx)) != len(idx):
+            raise ValueError("duplicate stream indices in the selection: every selected stream takes one row of the chunk")
+        return idx
+
+    def _call_subset(self, chunk, idx):
+        A = len(idx)
+        n = self._check_chunk(chunk, A)
+        with torch.no_grad():
+            ws = self._sub_ws.get(n)
+            if ws is None:
+                ws = self._sub_ws[n] = _SubsetWorkspace(self, n)
+            ws.chunk[:A].copy_(chunk.reshape(A, n * self.S))
+            ws.slots[:A].copy_(torch.tensor(idx, dtype=torch.int32))
+            if self.chunk_size is None:
+                self.chunk_size = n * self.S
+            if self.record and n * self.S == self.chunk_size:
+                flat = self.model.flat_parameters()
+                if self._sub_flat is not flat:                                  # model.to() since the recordings: their pointers are stale
+                    self._sub_seqs.clear()
+                    self._sub_flat = flat
+                seq = self._sub_seqs.get(A)
+                if seq is None:
+                    seq = sepkernels.Sequence()
+                    with sepkernels.recording(seq):
+                        self._step(ws.views(A), n, A, ws.slots)
+                    self._sub_seqs[A] = seq
+                    while len(self._sub_seqs) > self.max_recordings:           # a recording is a launch list: nothing on the device goes with it
+                        self._sub_seqs.popitem(last=False)
+                else:
+                    self._sub_seqs.move_to_end(A)
+                    seq.run()
+            else:
+                self._step(ws.views(A), n, A, ws.slots)
+            return ws.out[:A].clone()
+
     # ------------------------------------------------------------------ the chunk step
-    def _check_chunk(self, chunk):
-        if not torch.is_tensor(chunk) or chunk.dim() != 3 or chunk.shape[0] != self.num_streams or chunk.shape[1] != 1:
+    def _check_chunk(self, chunk, rows=None):
+        if rows is not None and (not torch.is_tensor(chunk) or chunk.dim() != 3 or chunk.shape[0] != rows or chunk.shape[1] != 1):
+            raise ValueError("a chunk for {} selected streams is ({}, 1, k*{}) (got {})".format(rows, rows, self.S, tuple(getattr(chunk, "shape", ()))))
+        if rows is None and (not torch.is_tensor(chunk) or chunk.dim() != 3 or chunk.shape[0] != self.num_streams or chunk.shape[1] != 1):
             raise ValueError("a chunk is (num_streams={}, 1, k*{}) (got {})".format(self.num_streams, self.S, tuple(getattr(chunk, "shape", ()))))
         T = chunk.shape[-1]
         if T == 0 or T % self.S:
@@ -174,11 +295,19 @@ class OnlineSeparator:
             raise ValueError("the chunk must be on {} in {} like the separator's state (got {} {})".format(self.device, self.dtype, chunk.device, chunk.dtype))
         return T // self.S
 
-    def _step(self, ws, n):
-        """one chunk of n frames of every stream: ~5 launches per TCN layer plus encoder, norm, bottleneck, mask, decoder and advance"""
+    def _step(self, ws, n, blocks=None, slots=None):
+        """one chunk of n frames of every stream: ~5 launches per TCN layer plus encoder, norm, bottleneck, mask, decoder and advance.
+        With `slots` (device int32): of the `blocks` streams it names, through the sep_online_*_sel entry points"""
         K = backend()
         model, sep = self.model, self.model.separator
         Bs, L, S, N, H, Bn, Sc, n_src = self.num_streams, self.L, self.S, self.N, self.H, self.Bn, self.Sc, self.n_src
+        if slots is None:
+            encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd, K.online_cln_fwd, K.online_depthwise_fwd, K.online_decoder_fwd,
+                                                                  K.online_advance, ())
+        else:
+            encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd_sel, K.online_cln_fwd_sel, K.online_depthwise_fwd_sel,
+                                                                  K.online_decoder_fwd_sel, K.online_advance_sel, (slots,))
+            Bs = blocks
         T, ldt = Bs * n, ws.ldt
         keep = self.delay
         sums, sstride = self.sums.view(-1), 2 * self.n_norms
@@ -189,11 +318,11 @@ class OnlineSeparator:
             amax = ws.amax
 
         def cln(x, y, norm, alpha, i):
-            K.online_cln_fwd(x, alpha, norm.gamma.reshape(-1), norm.beta.reshape(-1), y, sums[2 * i:], sstride, self.frames, Bs, x.shape[0], n, ldt,
-                             norm.eps)
+            cln_fwd(x, alpha, norm.gamma.reshape(-1), norm.beta.reshape(-1), y, sums[2 * i:], sstride, self.frames, Bs, x.shape[0], n, ldt,
+                    norm.eps, *sel)
 
-        K.online_encoder_fwd(ws.chunk, model.encoder.conv1d.weight, self.carry if keep else None, self.carry_next if keep else None, ws.w, Bs, N, L, S,
-                             n, ldt, model.enc_nonlinear == "relu")
+        encoder(ws.chunk, model.encoder.conv1d.weight, self.carry if keep else None, self.carry_next if keep else None, ws.w, Bs, N, L, S,
+                n, ldt, model.enc_nonlinear == "relu", *sel)
         cln(ws.w, ws.wn, sep.norm1d, None, 0)
         K.pw_gemm(B=1, M=Bn, K=N, T=T, ldt=ldt, A=sep.bottleneck_conv1d.weight, X=ws.wn, Y=ws.xa, bias=sep.bottleneck_conv1d.bias, a_amax=amax)
         x, x_next = ws.xa, ws.xb
@@ -203,8 +332,8 @@ class OnlineSeparator:
             d, P = layer.dilation, layer.kernel_size
             K.pw_gemm(B=1, M=H, K=Bn, T=T, ldt=ldt, A=layer.bottleneck_conv1d.weight, X=x, Y=ws.ha, bias=layer.bottleneck_conv1d.bias, a_amax=amax)
             cln(ws.ha, ws.hb, layer.norm1d, layer.nonlinear1d.weight, 1 + 2 * li)
-            K.online_depthwise_fwd(ws.hb, dw.depthwise_conv1d.weight, dw.depthwise_conv1d.bias, rings[self.ring_offsets[li]:], self.ring_len, ws.ha,
-                                   Bs, H, n, ldt, P, d)
+            depthwise(ws.hb, dw.depthwise_conv1d.weight, dw.depthwise_conv1d.bias, rings[self.ring_offsets[li]:], self.ring_len, ws.ha,
+                      Bs, H, n, ldt, P, d, *sel)
             cln(ws.ha, ws.hb, dw.norm1d, dw.nonlinear1d.weight, 2 + 2 * li)
             out = dw.output_pointwise_conv1d if dw.dual_head else None
             self._heads(K, ws.hb, out, dw.skip_pointwise_conv1d, x, x_next, ws.total, li == 0, T, ldt, amax)
@@ -215,10 +344,10 @@ class OnlineSeparator:
                   pro_alpha=sep.prelu.weight, epi_flags=EPI_SIGMOID if model.mask_nonlinear == "sigmoid" else 0, a_amax=amax)
         if model.mask_nonlinear != "sigmoid":
             K.softmax_ch_fwd(ws.m, 1, M, T, ldt)
-        K.online_decoder_fwd(ws.w, ws.m, model.decoder.conv_transpose1d.weight, self.tail if keep else None, self.tail_next if keep else None, ws.out,
-                             Bs, n_src, N, L, S, n, ldt)
-        K.online_advance(self.frames, self.carry if keep else None, self.carry_next if keep else None, keep, self.tail if keep else None,
-                         self.tail_next if keep else None, n_src * keep, Bs, n)
+        decoder(ws.w, ws.m, model.decoder.conv_transpose1d.weight, self.tail if keep else None, self.tail_next if keep else None, ws.out,
+                Bs, n_src, N, L, S, n, ldt, *sel)
+        advance(self.frames, self.carry if keep else None, self.carry_next if keep else None, keep, self.tail if keep else None,
+                self.tail_next if keep else None, n_src * keep, Bs, n, *sel)
 
     @staticmethod
     def _heads(K, v, out, skip, x_res, x_out, total, first, T, ldt, amax):
@@ -238,5 +367,5 @@ class OnlineSeparator:
         K.pw_gemm(B=1, M=Sc, K=H, T=T, ldt=ldt, A=Ws, X=v, Y=total, bias=bs, accumulate=int(not first), a_amax=amax)
 
     def launches_per_chunk(self):
-        """launches of one recorded chunk step (None before the first recorded chunk)"""
+        """launches of one recorded all-streams chunk step (None before the first recorded one; a subset step issues as many)"""
         return len(self._seq) if self._seq is not None else None

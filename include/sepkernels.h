@@ -587,7 +587,17 @@ int sep_axpby(const float* x, float a, const float* y, float b, float* out, int6
  *   sep_online_decoder_fwd    out[s][src][i] (i < n S) and tail_next[s][src][i - n S] = tail[s][src][i] (i < L - S) + sum over the frames f of the
  *                             chunk with f S <= i < f S + L of sum_nb w[nb][s n + f] mask[src N + nb][s n + f] D[nb][i - f S].
  *   sep_online_advance        frames += n; carry <- carry_next; tail <- tail_next (carry_len, tail_len: floats per stream).  The last launch of a chunk.
- *   sep_online_reset          for every stream s with mask[s] != 0: frames[s] = 0 and its slices of carry, sums, rings, tail (lengths per stream) = 0. */
+ *   sep_online_reset          for every stream s with mask[s] != 0: frames[s] = 0 and its slices of carry, sums, rings, tail (lengths per stream) = 0.
+ * SLOTS.  The state buffers may hold more streams than a pass runs.  Each sep_online_*_sel is its sibling plus `const int32_t* slots`, device
+ * memory of num_streams entries, and num_streams is then the number of COLUMN BLOCKS of the pass: block j (columns [j n, (j + 1) n), row j of
+ * chunk and of out) reads and updates the state of stream slots[j] -- the encoder its rows of carry / carry_next, the cLN its row of sums and
+ * frames[slots[j]], the depthwise kernel its row of ring, the decoder its rows of tail / tail_next; sep_online_advance_sel adds n to
+ * frames[slots[j]] and copies carry_next -> carry and tail_next -> tail for those rows only.  Rows of streams that slots does not name are
+ * neither read nor written, those of carry_next / tail_next included.  Entries must be distinct and inside the state buffers: the library
+ * cannot look at device memory, duplicates or entries out of range are undefined (sepkernels/online.py checks before it uploads).  The list
+ * is read when the kernels run, so a recorded pass replays for whatever selection of num_streams streams the buffer holds by then.  Both
+ * forms are instances of the same kernels (the indirection is a template argument); the plain entry points compute what they did before the
+ * _sel ones existed, bit for bit. */
 int sep_online_encoder_fwd(const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N, int L, int S,
                            int n, int ldt, int relu, sep_stream_t stream);
 int sep_online_cln_fwd(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums, int sums_stride,
@@ -600,6 +610,16 @@ int sep_online_advance(int64_t* frames, float* carry, const float* carry_next, i
                        int num_streams, int n, sep_stream_t stream);
 int sep_online_reset(const uint8_t* mask, int num_streams, int64_t* frames, float* carry, int carry_len, double* sums, int sums_len, float* rings,
                      int64_t rings_len, float* tail, int tail_len, sep_stream_t stream);
+int sep_online_encoder_fwd_sel(const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N, int L,
+                               int S, int n, int ldt, int relu, const int32_t* slots, sep_stream_t stream);
+int sep_online_cln_fwd_sel(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums, int sums_stride,
+                           const int64_t* frames, int num_streams, int C, int n, int ldt, float eps, const int32_t* slots, sep_stream_t stream);
+int sep_online_depthwise_fwd_sel(const float* x, const float* w, const float* bias, float* ring, int64_t ring_stride, float* y, int num_streams,
+                                 int C, int n, int ldt, int P, int dilation, const int32_t* slots, sep_stream_t stream);
+int sep_online_decoder_fwd_sel(const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out, int num_streams,
+                               int n_src, int N, int L, int S, int n, int ldt, const int32_t* slots, sep_stream_t stream);
+int sep_online_advance_sel(int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next, int tail_len,
+                           int num_streams, int n, const int32_t* slots, sep_stream_t stream);
 
 /* ---- the causal TCN layer's first norm folded into its depthwise convolution (ABI 23, additive; csrc/causal.hip) ------------------------
  * The first cLN of a causal layer (tdcn.py:107-147) feeds only the depthwise convolution, so its output v1 need not exist in memory:

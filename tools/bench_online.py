@@ -7,7 +7,11 @@ seeded default weights) separating `streams` concurrent 8 kHz streams chunk by c
     rtf / eager_rtf                           median chunk time / chunk duration (real time: < 1)
     launches_per_chunk, state_bytes, frames_per_s (encoder frames of all streams per second of the recorded step)
 
-    python tools/bench_online.py [--streams 1,16,64,256,1024] [--chunks 80,160,800] [--reps 200] [--eager-reps 200] [--out FILE]
+With --active A1,A2,... every (streams, chunk) configuration is followed by one line per A <= streams with "active": A -- subset calls
+sep(chunk, streams=idx) for A of the `streams` slots, a FRESH selection (A distinct slots in random order, drawn before the clock starts) at every
+call, the upload of the slot list inside the timed span; same fields, state_bytes still that of all slots, frames_per_s of the A streams.
+
+    python tools/bench_online.py [--streams 1,16,64,256,1024] [--chunks 80,160,800] [--active 64,256] [--reps 200] [--eager-reps 200] [--out FILE]
 """
 import argparse
 import json
@@ -25,14 +29,17 @@ PAPER = dict(n_basis=512, kernel_size=16, stride=8, enc_basis="trainable", dec_b
 RATE = 8000
 
 
-def _times(torch, sep, x, reps, warm):
-    for _ in range(warm):
-        sep(x)
+def _times(torch, sep, x, reps, warm, active=None):
+    """active: None, or the number of slots of a subset call; every call then names a fresh selection"""
+    g = torch.Generator().manual_seed(1)
+    picks = [torch.randperm(sep.num_streams, generator=g)[:active].tolist() if active else None for _ in range(warm + reps)]
+    for k in range(warm):
+        sep(x, picks[k]) if active else sep(x)
     torch.cuda.synchronize()
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
-    for a, b in ev:
+    for k, (a, b) in enumerate(ev):
         a.record()
-        sep(x)
+        sep(x, picks[warm + k]) if active else sep(x)
         b.record()
         b.synchronize()
     ms = sorted(a.elapsed_time(b) for a, b in ev)
@@ -43,6 +50,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", default="1,16,64,256,1024")
     ap.add_argument("--chunks", default="80,160,800")
+    ap.add_argument("--active", default="", help="also time subset calls with this many of the slots, e.g. 64,256")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--eager-reps", type=int, default=200)
     ap.add_argument("--out", default=None, help="also write the lines to this file")
@@ -71,6 +79,17 @@ def main():
                        device=torch.cuda.get_device_name(0))
             print(json.dumps(row), flush=True)
             lines.append(row)
+            for A in [int(v) for v in args.active.split(",") if v]:
+                if A > B:
+                    continue
+                xa = x[:A].contiguous()
+                med, p99 = _times(torch, rec, xa, args.reps, 5, active=A)
+                emed, ep99 = _times(torch, eager, xa, args.eager_reps, 3, active=A)
+                sub = dict(row, active=A, chunk_ms_median=round(med, 4), chunk_ms_p99=round(p99, 4), eager_ms_median=round(emed, 4),
+                           eager_ms_p99=round(ep99, 4), rtf=round(med / dur_ms, 4), eager_rtf=round(emed / dur_ms, 4),
+                           frames_per_s=round(A * (chunk // PAPER["stride"]) / (med / 1000.0), 1))
+                print(json.dumps(sub), flush=True)
+                lines.append(sub)
             del rec, eager, x
             torch.cuda.empty_cache()
     if args.out:
