@@ -14,6 +14,9 @@
 // Every entry point of a chunk has a sibling sep_online_*_sel that takes `const int32_t* slots` (device memory, num_streams distinct entries):
 // the pass then has num_streams column blocks and block j works on the state rows of stream slots[j], so a separator with many slots runs
 // a chunk of the few that have audio.  Both forms are the same kernel templates; without a slot list block j works on stream j.
+// RAGGED.  A third form sep_online_*_rag takes the slot list plus `const int32_t* offs` (device memory, num_streams + 1 increasing entries,
+// offs[0] = 0): column block j is [offs[j], offs[j + 1]), so every stream of a pass brings its own number of frames n_j >= 1, and `n` is n_cap,
+// the row pitch of chunk / out in hops.  The lengths are read when the kernels run, so a recorded pass replays for other lengths.
 // Everything that changes from chunk to chunk (frame counters, running sums, histories, carries, tails) lives in device memory, so a
 // recorded chunk step (sep_run_sequence) replays correctly.  No atomics: every result is formed in a fixed order, replays are bitwise.
 // State that is read and written by the same launch is owned by ONE workgroup that reads before a barrier and writes after it (cLN sums,
@@ -32,21 +35,42 @@ __device__ __forceinline__ int slot_of(const int32_t* __restrict__ slots, const 
     else return j;
 }
 
+// The column block that holds column col < offs[blocks]: the largest j with offs[j] <= col (offs increasing, offs[0] = 0).
+__device__ __forceinline__ int block_of(const int32_t* __restrict__ offs, const int blocks, const int col) {
+    int lo = 0, hi = blocks;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (offs[mid] <= col) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // w[nb][s n + f] = [ReLU] sum_k E[nb][k] ext_s[f S + k], ext_s = [carry_s (L - S) | chunk_s (n S)];  columns [num_streams n, ldt) = 0.
-// carry_next_s = ext_s[n S .. n S + L - S).
-template <bool SEL>
+// carry_next_s = ext_s[n S .. n S + L - S).  RAG: column block s is [offs[s], offs[s + 1]) with n_s frames, found by a search in offs; row s of chunk
+// has the pitch n S and only its first n_s S samples are read.
+template <bool SEL, bool RAG>
 __global__ __launch_bounds__(256) void online_encoder_kernel(const float* __restrict__ chunk, const float* __restrict__ E, const float* __restrict__ carry,
                                                              float* __restrict__ carry_next, float* __restrict__ w, int num_streams, int L, int S, int n,
-                                                             int ldt, int relu, const int32_t* __restrict__ slots) {
+                                                             int ldt, int relu, const int32_t* __restrict__ slots, const int32_t* __restrict__ offs) {
     const int nb = blockIdx.y;
     const int col = blockIdx.x * 256 + threadIdx.x;
     const int keep = L - S;
     const int64_t span = (int64_t)n * S;
-    const int cols = num_streams * n;
+    int cols;
+    if constexpr (RAG) cols = offs[num_streams];
+    else cols = num_streams * n;
     if (col < ldt) {
         float acc = 0.f;
         if (col < cols) {
-            const int s = col / n, f = col - s * n;
+            int s, f;
+            if constexpr (RAG) {
+                s = block_of(offs, num_streams, col);
+                f = col - offs[s];
+            } else {
+                s = col / n;
+                f = col - s * n;
+            }
             const float* cs = carry + (size_t)slot_of<SEL>(slots, s) * keep;
             const float* xs = chunk + (size_t)s * span;
             const float* e = E + (size_t)nb * L;
@@ -62,7 +86,8 @@ __global__ __launch_bounds__(256) void online_encoder_kernel(const float* __rest
     if (nb == 0 && keep > 0) {
         for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < (int64_t)num_streams * keep; g += (int64_t)gridDim.x * 256) {
             const int s = (int)(g / keep), i = (int)(g - (int64_t)s * keep);
-            const int64_t e = span + i;                                   // index into ext_s
+            int64_t e = span + i;                                         // index into ext_s
+            if constexpr (RAG) e = (int64_t)(offs[s + 1] - offs[s]) * S + i;
             const size_t st = (size_t)slot_of<SEL>(slots, s) * keep;
             carry_next[st + i] = e < keep ? carry[st + e] : chunk[(size_t)s * span + (e - keep)];
         }
@@ -75,18 +100,23 @@ constexpr int OC_CG = 8;          // channel groups: 8 x 32 = 256 threads
 // One workgroup per stream: tiles of 32 frames, column sums over the channels (fp32 per channel group -> fp64), an inclusive fp64 scan
 // over the tile on top of the running sums of everything the stream has seen, then the apply pass over the tile.  count = C (t + 1) with t
 // the absolute frame index (frames[s] + f).  The running sums are read by wave 0 at the start and written by lane 0 after the last barrier.
-template <bool SEL>
+// RAG: the stream's columns are [offs[s], offs[s + 1]), so n differs from workgroup to workgroup (it is uniform inside one: the barriers meet).
+template <bool SEL, bool RAG>
 __global__ __launch_bounds__(256) void online_cln_kernel(const float* __restrict__ x, const float* __restrict__ alpha, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float* __restrict__ y, double* __restrict__ sums, int sums_stride,
                                                          const int64_t* __restrict__ frames, int C, int n, int ldt, float eps,
-                                                         const int32_t* __restrict__ slots) {
+                                                         const int32_t* __restrict__ slots, const int32_t* __restrict__ offs) {
     __shared__ float red[2][OC_CG][OC_TW];
     __shared__ float mr[2][OC_TW];
     const int s = blockIdx.x, tid = threadIdx.x;
     const int fl = tid & (OC_TW - 1), cg = tid / OC_TW;
     const bool act = alpha != nullptr;
     const float al = act ? alpha[0] : 1.f;
-    const size_t col0 = (size_t)s * n;
+    size_t col0 = (size_t)s * n;
+    if constexpr (RAG) {
+        col0 = (size_t)offs[s];
+        n = offs[s + 1] - offs[s];
+    }
     const int st = slot_of<SEL>(slots, s);
     double* sm = sums + (size_t)st * sums_stride;
     double ca = 0.0, cq = 0.0, t0 = 0.0;
@@ -150,7 +180,9 @@ __global__ __launch_bounds__(256) void online_cln_kernel(const float* __restrict
         __syncthreads();                                                  // red / mr are rewritten by the next tile
     }
     if (s == (int)gridDim.x - 1) {                                        // the pad columns [num_streams n, ldt) of every row
-        const int cols = (int)gridDim.x * n, pad = ldt - cols;
+        int cols = (int)gridDim.x * n;
+        if constexpr (RAG) cols = offs[gridDim.x];
+        const int pad = ldt - cols;
         for (int64_t e = tid; e < (int64_t)C * pad; e += 256) {
             const int c = (int)(e / pad), j = (int)(e - (int64_t)c * pad);
             y[(size_t)c * ldt + cols + j] = 0.f;
@@ -165,16 +197,22 @@ __global__ __launch_bounds__(256) void online_cln_kernel(const float* __restrict
 // One workgroup per (channel, stream) row: the history is copied to LDS before the barrier, outputs and the new history are formed after
 // it from the LDS copy and the (unmodified) input, so a chunk shorter than the history (n < (P - 1) d) cannot race with itself.
 // y[f] = bias + sum_k w[k] ext[f + k d], ext = [history ((P - 1) d) | x (n)];  new history = ext[n .. n + (P - 1) d).
-template <bool SEL>
+// RAG: the row's columns are [offs[s], offs[s + 1]); n_s below and above (P - 1) d may meet in one launch.
+template <bool SEL, bool RAG>
 __global__ __launch_bounds__(256) void online_depthwise_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                                float* __restrict__ ring, int64_t ring_stride, float* __restrict__ y, int n, int ldt, int P, int d,
-                                                               const int32_t* __restrict__ slots) {
+                                                               const int32_t* __restrict__ slots, const int32_t* __restrict__ offs) {
     extern __shared__ float hist[];
     const int c = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
     const int D = (P - 1) * d;
     float* rg = ring + (size_t)slot_of<SEL>(slots, s) * ring_stride + (size_t)c * D;
-    const float* xr = x + (size_t)c * ldt + (size_t)s * n;
-    float* yr = y + (size_t)c * ldt + (size_t)s * n;
+    size_t col0 = (size_t)s * n;
+    if constexpr (RAG) {
+        col0 = (size_t)offs[s];
+        n = offs[s + 1] - offs[s];
+    }
+    const float* xr = x + (size_t)c * ldt + col0;
+    float* yr = y + (size_t)c * ldt + col0;
     for (int i = tid; i < D; i += 256) hist[i] = rg[i];
     __syncthreads();
     const float b = bias ? bias[c] : 0.f;
@@ -191,46 +229,63 @@ __global__ __launch_bounds__(256) void online_depthwise_kernel(const float* __re
         const int e = n + i;
         rg[i] = e < D ? hist[e] : xr[e - D];
     }
-    if (s == (int)gridDim.y - 1)
-        for (int t = (int)gridDim.y * n + tid; t < ldt; t += 256) y[(size_t)c * ldt + t] = 0.f;
+    if (s == (int)gridDim.y - 1) {
+        int cols = (int)gridDim.y * n;
+        if constexpr (RAG) cols = offs[gridDim.y];
+        for (int t = cols + tid; t < ldt; t += 256) y[(size_t)c * ldt + t] = 0.f;
+    }
 }
 
 // Thread per output sample i of [0, n S + L - S) of (stream, source): the old tail plus the overlap-add of the frames that cover i
-// (f S <= i < f S + L), latent = w * mask.  i < n S goes to out, the rest to tail_next.
-template <bool SEL>
+// (f S <= i < f S + L), latent = w * mask.  i < n S goes to out, the rest to tail_next.  RAG: the grid covers n_cap S + L - S samples, the stream has
+// n_s frames at columns offs[s] ..; its row of out has the pitch n_cap S and is written as zero from n_s S on.
+template <bool SEL, bool RAG>
 __global__ __launch_bounds__(256) void online_decoder_kernel(const float* __restrict__ w, const float* __restrict__ mask, const float* __restrict__ Dm,
                                                              const float* __restrict__ tail, float* __restrict__ tail_next, float* __restrict__ out,
-                                                             int n_src, int N, int L, int S, int n, int ldt, const int32_t* __restrict__ slots) {
+                                                             int n_src, int N, int L, int S, int n, int ldt, const int32_t* __restrict__ slots,
+                                                             const int32_t* __restrict__ offs) {
     const int src = blockIdx.y, s = blockIdx.z;
     const int keep = L - S;
+    const int pitch = n * S;                                              // samples per row of out
+    size_t col0 = (size_t)s * n;
+    if constexpr (RAG) {
+        col0 = (size_t)offs[s];
+        n = offs[s + 1] - offs[s];
+    }
     const int span = n * S;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= span + keep) return;
     const size_t row = (size_t)s * n_src + src;
+    if constexpr (RAG) {                                                  // a thread with span <= i < span + keep stores this zero AND goes on to the
+        if (i >= span && i < pitch) out[row * pitch + i] = 0.f;           // tail below: two different destinations, so the return stays behind the store
+    }
+    if (i >= span + keep) return;
     const size_t trow = (size_t)slot_of<SEL>(slots, s) * n_src + src;           // the stream's row of tail / tail_next
     float acc = i < keep ? tail[trow * keep + i] : 0.f;
     const int f_hi = (i / S) < n - 1 ? (i / S) : n - 1;
     const int f_lo = i - L + 1 > 0 ? (i - L + S) / S : 0;
     for (int f = f_lo; f <= f_hi; ++f) {
         const int k = i - f * S;
-        const size_t col = (size_t)s * n + f;
+        const size_t col = col0 + f;
         for (int nb = 0; nb < N; ++nb) {
             const float lat = w[(size_t)nb * ldt + col] * mask[((size_t)src * N + nb) * ldt + col];
             acc = fmaf(lat, Dm[(size_t)nb * L + k], acc);
         }
     }
-    if (i < span) out[row * span + i] = acc;
+    if (i < span) out[row * pitch + i] = acc;
     else tail_next[trow * keep + (i - span)] = acc;
 }
 
-template <bool SEL>
+template <bool SEL, bool RAG>
 __global__ __launch_bounds__(256) void online_advance_kernel(int64_t* __restrict__ frames, float* __restrict__ carry, const float* __restrict__ carry_next,
                                                              int64_t carry_total, float* __restrict__ tail, const float* __restrict__ tail_next,
                                                              int64_t tail_total, int num_streams, int n, int carry_len, int tail_len,
-                                                             const int32_t* __restrict__ slots) {
+                                                             const int32_t* __restrict__ slots, const int32_t* __restrict__ offs) {
     if constexpr (SEL) {                                                  // element g of column block g / len -> the same element of its stream's row
         for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < carry_total || g < tail_total || g < num_streams; g += (int64_t)gridDim.x * 256) {
-            if (g < num_streams) frames[slots[g]] += n;
+            if (g < num_streams) {
+                if constexpr (RAG) frames[slots[g]] += offs[g + 1] - offs[g];
+                else frames[slots[g]] += n;
+            }
             if (g < carry_total) {
                 const int64_t j = g / carry_len, e = (int64_t)slots[j] * carry_len + (g - j * carry_len);
                 carry[e] = carry_next[e];
@@ -267,62 +322,66 @@ inline int ceil_div_i(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 }  // namespace
 
-// The launchers behind both forms of an entry point: `who` names the caller in its errors, slots == nullptr is the plain form.
+// The launchers behind the three forms of an entry point: `who` names the caller in its errors, slots == nullptr is the plain form, offs != nullptr
+// (with slots) the ragged one, whose n is n_cap.
 static int online_encoder(const char* who, const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N,
-                          int L, int S, int n, int ldt, int relu, const int32_t* slots, sep_stream_t stream) {
+                          int L, int S, int n, int ldt, int relu, const int32_t* slots, const int32_t* offs, sep_stream_t stream) {
     SEP_REQUIRE(chunk && E && w && num_streams > 0 && N > 0 && S > 0 && L >= S && L % S == 0 && n > 0, "%s: bad arguments", who);
     SEP_REQUIRE((carry && carry_next) || L == S, "%s: carry buffers missing", who);
-    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0 && N <= 65535, "%s: bad sizes (streams=%d n=%d ldt=%d N=%d)", who, num_streams, n, ldt,
-                N);
-    const auto kern = slots ? online_encoder_kernel<true> : online_encoder_kernel<false>;
+    SEP_REQUIRE((int64_t)num_streams * (offs ? 1 : n) <= ldt && ldt % 128 == 0 && N <= 65535, "%s: bad sizes (streams=%d n=%d ldt=%d N=%d)", who,
+                num_streams, n, ldt, N);
+    const auto kern = offs ? online_encoder_kernel<true, true> : slots ? online_encoder_kernel<true, false> : online_encoder_kernel<false, false>;
     hipLaunchKernelGGL(kern, dim3(ceil_div_i(ldt, 256), N), dim3(256), 0, (hipStream_t)stream, chunk, E, carry, carry_next, w,
-                       num_streams, L, S, n, ldt, relu, slots);
+                       num_streams, L, S, n, ldt, relu, slots, offs);
     SEP_CHECK_LAUNCH(who);
     return 0;
 }
 
 static int online_cln(const char* who, const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums, int sums_stride,
-                      const int64_t* frames, int num_streams, int C, int n, int ldt, float eps, const int32_t* slots, sep_stream_t stream) {
+                      const int64_t* frames, int num_streams, int C, int n, int ldt, float eps, const int32_t* slots, const int32_t* offs,
+                      sep_stream_t stream) {
     SEP_REQUIRE(x && gamma && beta && y && sums && frames && num_streams > 0 && C > 0 && n > 0 && sums_stride >= 2, "%s: bad arguments", who);
     SEP_REQUIRE(x != y, "%s: y may not alias x", who);
-    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0, "%s: bad sizes (streams=%d n=%d ldt=%d)", who, num_streams, n, ldt);
-    const auto kern = slots ? online_cln_kernel<true> : online_cln_kernel<false>;
+    SEP_REQUIRE((int64_t)num_streams * (offs ? 1 : n) <= ldt && ldt % 128 == 0, "%s: bad sizes (streams=%d n=%d ldt=%d)", who, num_streams, n, ldt);
+    const auto kern = offs ? online_cln_kernel<true, true> : slots ? online_cln_kernel<true, false> : online_cln_kernel<false, false>;
     hipLaunchKernelGGL(kern, dim3(num_streams), dim3(256), 0, (hipStream_t)stream, x, alpha, gamma, beta, y, sums, sums_stride, frames,
-                       C, n, ldt, eps, slots);
+                       C, n, ldt, eps, slots, offs);
     SEP_CHECK_LAUNCH(who);
     return 0;
 }
 
 static int online_depthwise(const char* who, const float* x, const float* w, const float* bias, float* ring, int64_t ring_stride, float* y,
-                            int num_streams, int C, int n, int ldt, int P, int dilation, const int32_t* slots, sep_stream_t stream) {
+                            int num_streams, int C, int n, int ldt, int P, int dilation, const int32_t* slots, const int32_t* offs,
+                            sep_stream_t stream) {
     SEP_REQUIRE(x && w && ring && y && x != y && num_streams > 0 && num_streams <= 65535 && C > 0 && n > 0 && P >= 2 && dilation > 0,
                 "%s: bad arguments", who);
     const int64_t D = (int64_t)(P - 1) * dilation;
     SEP_REQUIRE(D <= 16384, "%s: history of %lld frames exceeds LDS", who, (long long)D);
     SEP_REQUIRE(ring_stride >= (int64_t)C * D, "%s: ring_stride %lld < C (P - 1) d", who, (long long)ring_stride);
-    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0, "%s: bad sizes (streams=%d n=%d ldt=%d)", who, num_streams, n, ldt);
-    const auto kern = slots ? online_depthwise_kernel<true> : online_depthwise_kernel<false>;
+    SEP_REQUIRE((int64_t)num_streams * (offs ? 1 : n) <= ldt && ldt % 128 == 0, "%s: bad sizes (streams=%d n=%d ldt=%d)", who, num_streams, n, ldt);
+    const auto kern = offs ? online_depthwise_kernel<true, true> : slots ? online_depthwise_kernel<true, false> : online_depthwise_kernel<false, false>;
     hipLaunchKernelGGL(kern, dim3(C, num_streams), dim3(256), (size_t)D * sizeof(float), (hipStream_t)stream, x, w, bias, ring,
-                       ring_stride, y, n, ldt, P, dilation, slots);
+                       ring_stride, y, n, ldt, P, dilation, slots, offs);
     SEP_CHECK_LAUNCH(who);
     return 0;
 }
 
 static int online_decoder(const char* who, const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out,
-                          int num_streams, int n_src, int N, int L, int S, int n, int ldt, const int32_t* slots, sep_stream_t stream) {
+                          int num_streams, int n_src, int N, int L, int S, int n, int ldt, const int32_t* slots, const int32_t* offs,
+                          sep_stream_t stream) {
     SEP_REQUIRE(w && mask && D && out && num_streams > 0 && num_streams <= 65535 && n_src > 0 && n_src <= 65535 && N > 0 && S > 0 && L >= S &&
                 L % S == 0 && n > 0, "%s: bad arguments", who);
     SEP_REQUIRE((tail && tail_next) || L == S, "%s: tail buffers missing", who);
-    SEP_REQUIRE((int64_t)num_streams * n <= ldt && ldt % 128 == 0, "%s: bad sizes (streams=%d n=%d ldt=%d)", who, num_streams, n, ldt);
-    const auto kern = slots ? online_decoder_kernel<true> : online_decoder_kernel<false>;
+    SEP_REQUIRE((int64_t)num_streams * (offs ? 1 : n) <= ldt && ldt % 128 == 0, "%s: bad sizes (streams=%d n=%d ldt=%d)", who, num_streams, n, ldt);
+    const auto kern = offs ? online_decoder_kernel<true, true> : slots ? online_decoder_kernel<true, false> : online_decoder_kernel<false, false>;
     hipLaunchKernelGGL(kern, dim3(ceil_div_i((int64_t)n * S + L - S, 256), n_src, num_streams), dim3(256), 0, (hipStream_t)stream, w, mask,
-                       D, tail, tail_next, out, n_src, N, L, S, n, ldt, slots);
+                       D, tail, tail_next, out, n_src, N, L, S, n, ldt, slots, offs);
     SEP_CHECK_LAUNCH(who);
     return 0;
 }
 
 static int online_advance(const char* who, int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next,
-                          int tail_len, int num_streams, int n, const int32_t* slots, sep_stream_t stream) {
+                          int tail_len, int num_streams, int n, const int32_t* slots, const int32_t* offs, sep_stream_t stream) {
     SEP_REQUIRE(frames && num_streams > 0 && n > 0 && carry_len >= 0 && tail_len >= 0, "%s: bad arguments", who);
     SEP_REQUIRE((carry && carry_next) || carry_len == 0, "%s: carry buffers missing", who);
     SEP_REQUIRE((tail && tail_next) || tail_len == 0, "%s: tail buffers missing", who);
@@ -330,67 +389,102 @@ static int online_advance(const char* who, int64_t* frames, float* carry, const 
     int64_t most = ct > tt ? ct : tt;
     most = most > num_streams ? most : num_streams;
     const int grid = ceil_div_i(most, 256) > 1024 ? 1024 : ceil_div_i(most, 256);
-    const auto kern = slots ? online_advance_kernel<true> : online_advance_kernel<false>;
+    const auto kern = offs ? online_advance_kernel<true, true> : slots ? online_advance_kernel<true, false> : online_advance_kernel<false, false>;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, carry, carry_next, ct, tail, tail_next, tt,
-                       num_streams, n, carry_len, tail_len, slots);
+                       num_streams, n, carry_len, tail_len, slots, offs);
     SEP_CHECK_LAUNCH(who);
     return 0;
 }
 
 extern "C" int sep_online_encoder_fwd(const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N,
                                       int L, int S, int n, int ldt, int relu, sep_stream_t stream) {
-    return online_encoder("sep_online_encoder_fwd", chunk, E, carry, carry_next, w, num_streams, N, L, S, n, ldt, relu, nullptr, stream);
+    return online_encoder("sep_online_encoder_fwd", chunk, E, carry, carry_next, w, num_streams, N, L, S, n, ldt, relu, nullptr, nullptr, stream);
 }
 
 extern "C" int sep_online_encoder_fwd_sel(const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N,
                                           int L, int S, int n, int ldt, int relu, const int32_t* slots, sep_stream_t stream) {
     SEP_REQUIRE(slots, "sep_online_encoder_fwd_sel: slots missing");
-    return online_encoder("sep_online_encoder_fwd_sel", chunk, E, carry, carry_next, w, num_streams, N, L, S, n, ldt, relu, slots, stream);
+    return online_encoder("sep_online_encoder_fwd_sel", chunk, E, carry, carry_next, w, num_streams, N, L, S, n, ldt, relu, slots, nullptr, stream);
 }
 
 extern "C" int sep_online_cln_fwd(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums, int sums_stride,
                                   const int64_t* frames, int num_streams, int C, int n, int ldt, float eps, sep_stream_t stream) {
-    return online_cln("sep_online_cln_fwd", x, alpha, gamma, beta, y, sums, sums_stride, frames, num_streams, C, n, ldt, eps, nullptr, stream);
+    return online_cln("sep_online_cln_fwd", x, alpha, gamma, beta, y, sums, sums_stride, frames, num_streams, C, n, ldt, eps, nullptr, nullptr, stream);
 }
 
 extern "C" int sep_online_cln_fwd_sel(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums,
                                       int sums_stride, const int64_t* frames, int num_streams, int C, int n, int ldt, float eps, const int32_t* slots,
                                       sep_stream_t stream) {
     SEP_REQUIRE(slots, "sep_online_cln_fwd_sel: slots missing");
-    return online_cln("sep_online_cln_fwd_sel", x, alpha, gamma, beta, y, sums, sums_stride, frames, num_streams, C, n, ldt, eps, slots, stream);
+    return online_cln("sep_online_cln_fwd_sel", x, alpha, gamma, beta, y, sums, sums_stride, frames, num_streams, C, n, ldt, eps, slots, nullptr, stream);
 }
 
 extern "C" int sep_online_depthwise_fwd(const float* x, const float* w, const float* bias, float* ring, int64_t ring_stride, float* y, int num_streams,
                                         int C, int n, int ldt, int P, int dilation, sep_stream_t stream) {
-    return online_depthwise("sep_online_depthwise_fwd", x, w, bias, ring, ring_stride, y, num_streams, C, n, ldt, P, dilation, nullptr, stream);
+    return online_depthwise("sep_online_depthwise_fwd", x, w, bias, ring, ring_stride, y, num_streams, C, n, ldt, P, dilation, nullptr, nullptr, stream);
 }
 
 extern "C" int sep_online_depthwise_fwd_sel(const float* x, const float* w, const float* bias, float* ring, int64_t ring_stride, float* y,
                                             int num_streams, int C, int n, int ldt, int P, int dilation, const int32_t* slots, sep_stream_t stream) {
     SEP_REQUIRE(slots, "sep_online_depthwise_fwd_sel: slots missing");
-    return online_depthwise("sep_online_depthwise_fwd_sel", x, w, bias, ring, ring_stride, y, num_streams, C, n, ldt, P, dilation, slots, stream);
+    return online_depthwise("sep_online_depthwise_fwd_sel", x, w, bias, ring, ring_stride, y, num_streams, C, n, ldt, P, dilation, slots, nullptr, stream);
 }
 
 extern "C" int sep_online_decoder_fwd(const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out, int num_streams,
                                       int n_src, int N, int L, int S, int n, int ldt, sep_stream_t stream) {
-    return online_decoder("sep_online_decoder_fwd", w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n, ldt, nullptr, stream);
+    return online_decoder("sep_online_decoder_fwd", w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n, ldt, nullptr, nullptr, stream);
 }
 
 extern "C" int sep_online_decoder_fwd_sel(const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out,
                                           int num_streams, int n_src, int N, int L, int S, int n, int ldt, const int32_t* slots, sep_stream_t stream) {
     SEP_REQUIRE(slots, "sep_online_decoder_fwd_sel: slots missing");
-    return online_decoder("sep_online_decoder_fwd_sel", w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n, ldt, slots, stream);
+    return online_decoder("sep_online_decoder_fwd_sel", w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n, ldt, slots, nullptr, stream);
 }
 
 extern "C" int sep_online_advance(int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next,
                                   int tail_len, int num_streams, int n, sep_stream_t stream) {
-    return online_advance("sep_online_advance", frames, carry, carry_next, carry_len, tail, tail_next, tail_len, num_streams, n, nullptr, stream);
+    return online_advance("sep_online_advance", frames, carry, carry_next, carry_len, tail, tail_next, tail_len, num_streams, n, nullptr, nullptr, stream);
 }
 
 extern "C" int sep_online_advance_sel(int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next,
                                       int tail_len, int num_streams, int n, const int32_t* slots, sep_stream_t stream) {
     SEP_REQUIRE(slots, "sep_online_advance_sel: slots missing");
-    return online_advance("sep_online_advance_sel", frames, carry, carry_next, carry_len, tail, tail_next, tail_len, num_streams, n, slots, stream);
+    return online_advance("sep_online_advance_sel", frames, carry, carry_next, carry_len, tail, tail_next, tail_len, num_streams, n, slots, nullptr, stream);
+}
+
+extern "C" int sep_online_encoder_fwd_rag(const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N,
+                                          int L, int S, int n_cap, int ldt, int relu, const int32_t* slots, const int32_t* offs, sep_stream_t stream) {
+    SEP_REQUIRE(slots && offs, "sep_online_encoder_fwd_rag: slots / offs missing");
+    return online_encoder("sep_online_encoder_fwd_rag", chunk, E, carry, carry_next, w, num_streams, N, L, S, n_cap, ldt, relu, slots, offs, stream);
+}
+
+extern "C" int sep_online_cln_fwd_rag(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums,
+                                      int sums_stride, const int64_t* frames, int num_streams, int C, int n_cap, int ldt, float eps,
+                                      const int32_t* slots, const int32_t* offs, sep_stream_t stream) {
+    SEP_REQUIRE(slots && offs, "sep_online_cln_fwd_rag: slots / offs missing");
+    return online_cln("sep_online_cln_fwd_rag", x, alpha, gamma, beta, y, sums, sums_stride, frames, num_streams, C, n_cap, ldt, eps, slots, offs, stream);
+}
+
+extern "C" int sep_online_depthwise_fwd_rag(const float* x, const float* w, const float* bias, float* ring, int64_t ring_stride, float* y,
+                                            int num_streams, int C, int n_cap, int ldt, int P, int dilation, const int32_t* slots,
+                                            const int32_t* offs, sep_stream_t stream) {
+    SEP_REQUIRE(slots && offs, "sep_online_depthwise_fwd_rag: slots / offs missing");
+    return online_depthwise("sep_online_depthwise_fwd_rag", x, w, bias, ring, ring_stride, y, num_streams, C, n_cap, ldt, P, dilation, slots, offs,
+                            stream);
+}
+
+extern "C" int sep_online_decoder_fwd_rag(const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out,
+                                          int num_streams, int n_src, int N, int L, int S, int n_cap, int ldt, const int32_t* slots,
+                                          const int32_t* offs, sep_stream_t stream) {
+    SEP_REQUIRE(slots && offs, "sep_online_decoder_fwd_rag: slots / offs missing");
+    return online_decoder("sep_online_decoder_fwd_rag", w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n_cap, ldt, slots, offs, stream);
+}
+
+extern "C" int sep_online_advance_rag(int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next,
+                                      int tail_len, int num_streams, int n_cap, const int32_t* slots, const int32_t* offs, sep_stream_t stream) {
+    SEP_REQUIRE(slots && offs, "sep_online_advance_rag: slots / offs missing");
+    return online_advance("sep_online_advance_rag", frames, carry, carry_next, carry_len, tail, tail_next, tail_len, num_streams, n_cap, slots, offs,
+                          stream);
 }
 
 extern "C" int sep_online_reset(const uint8_t* mask, int num_streams, int64_t* frames, float* carry, int carry_len, double* sums, int sums_len,

@@ -463,7 +463,14 @@ class ConvTasNet(nn.Module):
         an integer tensor or a bool mask) and advances only those, at the cost of A streams; flush(streams) returns and resets only those; so
         the equality above holds for every stream by itself, whichever others took part in which calls.  Duplicate or out-of-range indices, an
         empty selection, a mask of the wrong length and a chunk whose rows do not match the selection are ValueErrors.  Subset steps at
-        `chunk_size` are recorded per number of selected streams; `max_recordings` (default 8) of them are kept, least recently used out first."""
+        `chunk_size` are recorded per number of selected streams; `max_recordings` (default 8) of them are kept, least recently used out first.
+        A call may be ragged: sep(chunk, streams=[7, 2, 5], lengths=[80, 8, 24]) takes (A, 1, W) with `lengths` in samples (a list or an integer
+        tensor; positive multiples of the stride, <= W), reads lengths[j] samples of row j, advances that stream by lengths[j] / stride frames and
+        returns (A, n_sources, W) with row j zero beyond lengths[j]; streams=None with num_streams lengths is the all-streams ragged call; and
+        sep([x0, x1, ...], streams=idx) takes a list of (1, k_j * stride) or (k_j * stride,) tensors and returns a list of (n_sources, k_j * stride).
+        The equality above still holds per stream.  A wrong count of lengths, a length that is zero, negative, not a multiple of the stride or
+        > W, and a non-integer tensor are ValueErrors.  Ragged steps with W == `chunk_size` are recorded per (A, round_up(total frames, 128)) and
+        replayed for any lengths with that total, under the same `max_recordings` bound."""
         from sepkernels.online import OnlineSeparator
         return OnlineSeparator(self, num_streams=num_streams, chunk_size=chunk_size, record=record, max_recordings=max_recordings)
 

@@ -210,6 +210,12 @@ SIGNATURES = {
     "sep_online_depthwise_fwd_sel": [_vp] * 4 + [_L, _vp] + [_I] * 6 + [_vp, _vp],
     "sep_online_decoder_fwd_sel": [_vp] * 6 + [_I] * 7 + [_vp, _vp],
     "sep_online_advance_sel": [_vp] * 3 + [_I] + [_vp] * 2 + [_I] * 3 + [_vp, _vp],
+    # ... with a chunk length per stream (offs after slots; n is n_cap)
+    "sep_online_encoder_fwd_rag": [_vp] * 5 + [_I] * 7 + [_vp, _vp, _vp],
+    "sep_online_cln_fwd_rag": [_vp] * 6 + [_I, _vp] + [_I] * 4 + [_F, _vp, _vp, _vp],
+    "sep_online_depthwise_fwd_rag": [_vp] * 4 + [_L, _vp] + [_I] * 6 + [_vp, _vp, _vp],
+    "sep_online_decoder_fwd_rag": [_vp] * 6 + [_I] * 7 + [_vp, _vp, _vp],
+    "sep_online_advance_rag": [_vp] * 3 + [_I] + [_vp] * 2 + [_I] * 3 + [_vp, _vp, _vp],
     # the causal layer's first norm folded into its depthwise kernels (ABI 23, additive): csrc/causal.hip, sepkernels/causal.py
     "sep_cln_stats": [_vp] * 4 + [_I] * 4 + [_F, _vp, _vp],
     "sep_depthwise_cln_fwd": [_vp] * 9 + [_I] * 7 + [_vp],
@@ -811,6 +817,33 @@ class HipBackend:
         _check(load().sep_online_advance_sel(_ptr(frames, torch.int64), _ptr(carry, _f32), _ptr(carry_next, _f32), carry_len, _ptr(tail, _f32),
                                              _ptr(tail_next, _f32), tail_len, num_streams, n, _ptr(slots, torch.int32), _stream()),
                "sep_online_advance_sel")
+
+    # ... with a chunk length per stream: `offs` (int32, num_streams + 1 entries on the device) bounds the column block of every stream, n_cap is
+    # the row pitch of chunk / out in hops
+    def online_encoder_fwd_rag(self, chunk, E, carry, carry_next, w, num_streams, N, L, S, n_cap, ldt, relu, slots, offs):
+        _check(load().sep_online_encoder_fwd_rag(_ptr(chunk, _f32), _ptr(E, _f32), _ptr(carry, _f32), _ptr(carry_next, _f32), _ptr(w, _f32),
+                                                 num_streams, N, L, S, n_cap, ldt, int(relu), _ptr(slots, torch.int32), _ptr(offs, torch.int32),
+                                                 _stream()), "sep_online_encoder_fwd_rag")
+
+    def online_cln_fwd_rag(self, x, alpha, gamma, beta, y, sums, sums_stride, frames, num_streams, C, n_cap, ldt, eps, slots, offs):
+        _check(load().sep_online_cln_fwd_rag(_ptr(x, _f32), _ptr(alpha, _f32), _ptr(gamma, _f32), _ptr(beta, _f32), _ptr(y, _f32), _ptr(sums, _f64),
+                                             sums_stride, _ptr(frames, torch.int64), num_streams, C, n_cap, ldt, eps, _ptr(slots, torch.int32),
+                                             _ptr(offs, torch.int32), _stream()), "sep_online_cln_fwd_rag")
+
+    def online_depthwise_fwd_rag(self, x, w, bias, ring, ring_stride, y, num_streams, C, n_cap, ldt, P, dilation, slots, offs):
+        _check(load().sep_online_depthwise_fwd_rag(_ptr(x, _f32), _ptr(w, _f32), _ptr(bias, _f32), _ptr(ring, _f32), ring_stride, _ptr(y, _f32),
+                                                   num_streams, C, n_cap, ldt, P, dilation, _ptr(slots, torch.int32), _ptr(offs, torch.int32),
+                                                   _stream()), "sep_online_depthwise_fwd_rag")
+
+    def online_decoder_fwd_rag(self, w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n_cap, ldt, slots, offs):
+        _check(load().sep_online_decoder_fwd_rag(_ptr(w, _f32), _ptr(mask, _f32), _ptr(D, _f32), _ptr(tail, _f32), _ptr(tail_next, _f32),
+                                                 _ptr(out, _f32), num_streams, n_src, N, L, S, n_cap, ldt, _ptr(slots, torch.int32),
+                                                 _ptr(offs, torch.int32), _stream()), "sep_online_decoder_fwd_rag")
+
+    def online_advance_rag(self, frames, carry, carry_next, carry_len, tail, tail_next, tail_len, num_streams, n_cap, slots, offs):
+        _check(load().sep_online_advance_rag(_ptr(frames, torch.int64), _ptr(carry, _f32), _ptr(carry_next, _f32), carry_len, _ptr(tail, _f32),
+                                             _ptr(tail_next, _f32), tail_len, num_streams, n_cap, _ptr(slots, torch.int32), _ptr(offs, torch.int32),
+                                             _stream()), "sep_online_advance_rag")
 
 
 _backend = HipBackend()

@@ -40,6 +40,24 @@ replays for ANY selection of A slots.  One workspace per chunk length serves eve
 round_up(A n, 128) inside storage sized for all slots, and a recording per A holds a launch list only.  At most `max_recordings` (default 8)
 of them are kept, the least recently used one is dropped first -- a recording owns no device memory of its own, so dropping one is safe at
 any time and the next call of that A records again.  streams=None is the all-streams call: it issues exactly the launches it always did.
+
+Ragged calls.  With `lengths` every stream of a call brings its own number of samples, so one pass carries whatever each stream has right now:
+
+    y = sep(chunk, streams=[7, 2, 5], lengths=[80, 8, 24])   # chunk (3, 1, W), W a multiple of S; lengths in samples
+    ys = sep([x7, x2, x5], streams=[7, 2, 5])                # a list of (1, k_j S) or (k_j S,) tensors -> a list of (n_sources, k_j S)
+
+`lengths` has one entry per row (a list, or an integer tensor on any device), each a positive multiple of S and <= W.  Row j's samples beyond
+lengths[j] are ignored, the result is (A, n_sources, W) with row j zero beyond lengths[j], and slot streams[j] advances by lengths[j] / S frames.
+streams=None with `lengths` of num_streams entries is the all-streams ragged call.  The list form pads on the device to the longest piece and
+calls the tensor form.  The per-stream contract is unchanged, whatever lengths a slot and the others brought to which calls; flush and reset
+are untouched.  A wrong count of lengths, a length that is zero, negative, not a multiple of S or > W, and a non-integer tensor are ValueErrors
+that leave no trace in the state.  With lengths=None a call issues exactly the launches it did before; with `lengths` the ragged path always
+runs, even if all entries are equal.  The columns of a ragged pass are compact: block j is [offs[j], offs[j + 1]) with offs the running sum of
+the frame counts, ldt = round_up(offs[A], 128), and offs sits in a device buffer next to the slot list that is filled before every call (the
+sep_online_*_rag entry points read it when they run).  The step is the launch list of a subset step; its products run over T = ldt columns --
+the dead columns [offs[A], ldt) are zero wherever a state kernel wrote, only ever feed themselves, and no state kernel nor the decoder reads
+them -- so the launch arguments depend on (A, ldt, W) only: a ragged call with W == chunk_size is recorded per (A, ldt) and replayed for ANY
+lengths with that total, under the same `max_recordings` bound.  Other widths run eagerly.
 """
 import collections
 
@@ -89,13 +107,15 @@ class _SubsetWorkspace:
         self.chunk = torch.zeros(Bs, n * sep.S, **f)
         self.out = torch.zeros(Bs, sep.n_src, n * sep.S, **f)
         self.slots = torch.zeros(Bs, device=sep.device, dtype=torch.int32)
+        self.offs = torch.zeros(Bs + 1, device=sep.device, dtype=torch.int32)     # ragged calls: the column block of every stream
         self.amax = torch.zeros(1, **f)
         self.rows = dict(w=sep.N, wn=sep.N, xa=sep.Bn, xb=sep.Bn, ha=sep.H, hb=sep.H, total=sep.Sc, m=sep.n_src * sep.N)
         self.store = {k: torch.zeros(C * ldt, **f) for k, C in self.rows.items()}
 
-    def views(self, A):
+    def views(self, A, ldt=None):
+        """ldt: of a ragged call (round_up of the frames it carries, 128); None: of a call whose A streams bring n frames each"""
         v = _Views()
-        v.n, v.ldt = self.n, _round_up(A * self.n, 128)
+        v.n, v.ldt = self.n, _round_up(A * self.n, 128) if ldt is None else ldt
         for k, C in self.rows.items():
             setattr(v, k, self.store[k][:C * v.ldt].view(C, v.ldt))
         v.chunk, v.out, v.amax = self.chunk[:A], self.out[:A], self.amax
@@ -110,8 +130,8 @@ class OnlineSeparator:
     delay        L - S: output sample t + delay is the separated version of input sample t
     state_bytes  device memory of the per-stream state (carry, frame counter, cLN sums, depthwise histories, overlap-add tail)
 
-    max_recordings  how many recorded subset steps (one per number of selected streams A, at `chunk_size`) are kept; the least recently used
-                    one is dropped first and recorded again when that A comes back"""
+    max_recordings  how many recorded subset steps (one per number of selected streams A, at `chunk_size`) and ragged steps (one per (A, ldt)) are
+                    kept; the least recently used one is dropped first and recorded again when that A or (A, ldt) comes back"""
 
     def __init__(self, model, num_streams=1, chunk_size=None, record=True, max_recordings=8):
         if not model.causal:
@@ -162,14 +182,22 @@ class OnlineSeparator:
         self._ws = {}
         self._seq = self._seq_n = self._seq_flat = None
         self.max_recordings = int(max_recordings)
-        self._sub_ws = {}                                      # chunk frames n -> _SubsetWorkspace
-        self._sub_seqs = collections.OrderedDict()             # A -> Sequence of a subset step at chunk_size, least recently used first
+        self._sub_ws = {}                                      # chunk frames n (ragged calls: the row pitch in hops) -> _SubsetWorkspace
+        self._sub_seqs = collections.OrderedDict()             # A (subset step) or (A, ldt) (ragged step) -> Sequence at chunk_size, least recently used first
+        self.replays = collections.Counter()                   # recording key -> how often it was replayed
         self._sub_flat = None
 
     # ------------------------------------------------------------------ public
-    def __call__(self, chunk, streams=None):
+    def __call__(self, chunk, streams=None, lengths=None):
         """chunk (num_streams, 1, k S) -> (num_streams, n_sources, k S); with `streams` (indices in any order, an integer tensor or a bool mask)
-        chunk is (A, 1, k S) for the A selected streams in that order, only they advance, and the result is (A, n_sources, k S)"""
+        chunk is (A, 1, k S) for the A selected streams in that order, only they advance, and the result is (A, n_sources, k S).  With `lengths`
+        (samples per row, positive multiples of S, <= k S) row j brings lengths[j] samples, advances by lengths[j] / S frames and comes back zero
+        beyond lengths[j]; a list of (1, k_j S) or (k_j S,) tensors in place of chunk is that call on the pieces padded to the longest, and
+        returns a list of (n_sources, k_j S)"""
+        if isinstance(chunk, (list, tuple)):
+            return self._call_list(chunk, streams, lengths)
+        if lengths is not None:
+            return self._call_ragged(chunk, self._select(streams) if streams is not None else list(range(self.num_streams)), lengths)
         if streams is not None:
             return self._call_subset(chunk, self._select(streams))
         n = self._check_chunk(chunk)
@@ -280,6 +308,85 @@ class OnlineSeparator:
                 self._step(ws.views(A), n, A, ws.slots)
             return ws.out[:A].clone()
 
+    # ------------------------------------------------------------------ a call in which every stream brings its own length
+    def _frames_of(self, lengths, A, W):
+        """-> frames per row, checked"""
+        if torch.is_tensor(lengths):
+            if lengths.dtype == torch.bool or lengths.is_floating_point() or lengths.is_complex():
+                raise ValueError("lengths must be an integer tensor (got {})".format(lengths.dtype))
+            lengths = lengths.reshape(-1).tolist()
+        else:
+            lengths = list(lengths)
+            if any(isinstance(v, bool) or int(v) != v for v in lengths):
+                raise ValueError("lengths must be integers (got {})".format(lengths))
+            lengths = [int(v) for v in lengths]
+        if len(lengths) != A:
+            raise ValueError("{} lengths for {} rows of the chunk: every row takes one".format(len(lengths), A))
+        for v in lengths:
+            if v <= 0 or v % self.S or v > W:
+                raise ValueError("a length must be a positive multiple of the stride {} and at most the chunk's {} samples (got {})".format(self.S, W, v))
+        return [v // self.S for v in lengths]
+
+    def _call_ragged(self, chunk, idx, lengths):
+        A = len(idx)
+        cap = self._check_chunk(chunk, A)
+        W = cap * self.S
+        counts = self._frames_of(lengths, A, W)
+        offs = [0]
+        for k in counts:
+            offs.append(offs[-1] + k)
+        ldt = _round_up(offs[-1], 128)
+        with torch.no_grad():
+            ws = self._sub_ws.get(cap)                                          # shared with the uniform subset calls of this width
+            if ws is None:
+                ws = self._sub_ws[cap] = _SubsetWorkspace(self, cap)
+            ws.chunk[:A].copy_(chunk.reshape(A, W))
+            ws.slots[:A].copy_(torch.tensor(idx, dtype=torch.int32))
+            ws.offs[:A + 1].copy_(torch.tensor(offs, dtype=torch.int32))
+            if self.chunk_size is None:
+                self.chunk_size = W
+            if self.record and W == self.chunk_size:
+                flat = self.model.flat_parameters()
+                if self._sub_flat is not flat:                                  # model.to() since the recordings: their pointers are stale
+                    self._sub_seqs.clear()
+                    self._sub_flat = flat
+                key = (A, ldt)
+                seq = self._sub_seqs.get(key)
+                if seq is None:
+                    seq = sepkernels.Sequence()
+                    with sepkernels.recording(seq):
+                        self._step(ws.views(A, ldt), cap, A, ws.slots, ws.offs)
+                    self._sub_seqs[key] = seq
+                    while len(self._sub_seqs) > self.max_recordings:
+                        self._sub_seqs.popitem(last=False)
+                else:
+                    self._sub_seqs.move_to_end(key)
+                    seq.run()
+                    self.replays[key] += 1
+            else:
+                self._step(ws.views(A, ldt), cap, A, ws.slots, ws.offs)
+            return ws.out[:A].clone()
+
+    def _call_list(self, pieces, streams, lengths):
+        if lengths is not None:
+            raise ValueError("a list of pieces carries its own lengths: do not pass `lengths` with it")
+        idx = self._select(streams) if streams is not None else list(range(self.num_streams))
+        if len(pieces) != len(idx):
+            raise ValueError("{} pieces for {} selected streams: every stream takes one".format(len(pieces), len(idx)))
+        rows = []
+        for x in pieces:
+            if not torch.is_tensor(x) or x.dim() not in (1, 2) or (x.dim() == 2 and x.shape[0] != 1) or x.device != self.device or x.dtype != self.dtype:
+                raise ValueError("a piece is a (1, k*{}) or (k*{},) tensor on {} in {}".format(self.S, self.S, self.device, self.dtype))
+            rows.append(x.reshape(-1))
+        sizes = [r.numel() for r in rows]
+        if any(v <= 0 or v % self.S for v in sizes):
+            raise ValueError("a piece's length must be a positive multiple of the stride {} (got {})".format(self.S, sizes))
+        chunk = torch.zeros(len(rows), 1, max(sizes), device=self.device, dtype=self.dtype)
+        for j, r in enumerate(rows):
+            chunk[j, 0, :sizes[j]] = r
+        y = self._call_ragged(chunk, idx, sizes)
+        return [y[j, :, :sizes[j]] for j in range(len(rows))]
+
     # ------------------------------------------------------------------ the chunk step
     def _check_chunk(self, chunk, rows=None):
         if rows is not None and (not torch.is_tensor(chunk) or chunk.dim() != 3 or chunk.shape[0] != rows or chunk.shape[1] != 1):
@@ -295,20 +402,26 @@ class OnlineSeparator:
             raise ValueError("the chunk must be on {} in {} like the separator's state (got {} {})".format(self.device, self.dtype, chunk.device, chunk.dtype))
         return T // self.S
 
-    def _step(self, ws, n, blocks=None, slots=None):
+    def _step(self, ws, n, blocks=None, slots=None, offs=None):
         """one chunk of n frames of every stream: ~5 launches per TCN layer plus encoder, norm, bottleneck, mask, decoder and advance.
-        With `slots` (device int32): of the `blocks` streams it names, through the sep_online_*_sel entry points"""
+        With `slots` (device int32): of the `blocks` streams it names, through the sep_online_*_sel entry points.  With `offs` too (device
+        int32, blocks + 1 entries): stream j brings offs[j + 1] - offs[j] <= n frames, through the sep_online_*_rag entry points, and the
+        products run over all ws.ldt columns"""
         K = backend()
         model, sep = self.model, self.model.separator
         Bs, L, S, N, H, Bn, Sc, n_src = self.num_streams, self.L, self.S, self.N, self.H, self.Bn, self.Sc, self.n_src
         if slots is None:
             encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd, K.online_cln_fwd, K.online_depthwise_fwd, K.online_decoder_fwd,
                                                                   K.online_advance, ())
-        else:
+        elif offs is None:
             encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd_sel, K.online_cln_fwd_sel, K.online_depthwise_fwd_sel,
                                                                   K.online_decoder_fwd_sel, K.online_advance_sel, (slots,))
             Bs = blocks
-        T, ldt = Bs * n, ws.ldt
+        else:
+            encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd_rag, K.online_cln_fwd_rag, K.online_depthwise_fwd_rag,
+                                                                  K.online_decoder_fwd_rag, K.online_advance_rag, (slots, offs))
+            Bs = blocks
+        T, ldt = (Bs * n if offs is None else ws.ldt), ws.ldt
         keep = self.delay
         sums, sstride = self.sums.view(-1), 2 * self.n_norms
         amax = None

@@ -597,7 +597,21 @@ int sep_axpby(const float* x, float a, const float* y, float b, float* out, int6
  * cannot look at device memory, duplicates or entries out of range are undefined (sepkernels/online.py checks before it uploads).  The list
  * is read when the kernels run, so a recorded pass replays for whatever selection of num_streams streams the buffer holds by then.  Both
  * forms are instances of the same kernels (the indirection is a template argument); the plain entry points compute what they did before the
- * _sel ones existed, bit for bit. */
+ * _sel ones existed, bit for bit.
+ * RAGGED.  Each sep_online_*_rag is its _sel sibling plus `const int32_t* offs`, device memory of num_streams + 1 entries next to the slot list:
+ * column block j is [offs[j], offs[j + 1]) with offs[0] = 0, so stream slots[j] brings n_j = offs[j + 1] - offs[j] >= 1 frames of its own, the
+ * columns are compact, and ldt is a multiple of 128 >= offs[num_streams].  `n` becomes n_cap: the widest block allowed and the row pitch of
+ * chunk (num_streams, n_cap S) and out (num_streams, n_src, n_cap S) in hops.  The encoder reads the first n_j S samples of row j and nothing
+ * beyond (the rest may hold anything, NaN included), finds a column's block by a search in offs, and its carry_next is the last L - S samples
+ * of [carry | n_j S samples]; the cLN runs one workgroup per block over n_j frames with t = frames[slots[j]] + f; the depthwise kernel runs
+ * workgroup (channel, block), and n_j < (P - 1) d and n_j > (P - 1) d may meet in one launch; the decoder writes samples [0, n_j S) of row j,
+ * ZERO in [n_j S, n_cap S), and takes tail_next from position n_j S on; sep_online_advance_rag adds n_j to frames[slots[j]] and copies carry /
+ * tail back for the named rows only.  Every kernel that writes a matrix writes its columns [offs[num_streams], ldt) as zero.  Ownership is that
+ * of the _sel form: no atomics, rows of unnamed streams are neither read nor written (second buffers included).  slots is required (all
+ * streams: the identity list).  offs is read when the kernels run, so a recorded pass replays for other lengths with an ldt that still holds
+ * them.  The library cannot look at device memory: an offs that is not increasing, a block wider than n_cap or offs[num_streams] > ldt is
+ * undefined (sepkernels/online.py checks before it uploads).  The plain and _sel entry points stay the instances they were (the ragged path is
+ * a further template argument), bit for bit. */
 int sep_online_encoder_fwd(const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N, int L, int S,
                            int n, int ldt, int relu, sep_stream_t stream);
 int sep_online_cln_fwd(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums, int sums_stride,
@@ -620,6 +634,17 @@ int sep_online_decoder_fwd_sel(const float* w, const float* mask, const float* D
                                int n_src, int N, int L, int S, int n, int ldt, const int32_t* slots, sep_stream_t stream);
 int sep_online_advance_sel(int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next, int tail_len,
                            int num_streams, int n, const int32_t* slots, sep_stream_t stream);
+int sep_online_encoder_fwd_rag(const float* chunk, const float* E, const float* carry, float* carry_next, float* w, int num_streams, int N, int L,
+                               int S, int n_cap, int ldt, int relu, const int32_t* slots, const int32_t* offs, sep_stream_t stream);
+int sep_online_cln_fwd_rag(const float* x, const float* alpha, const float* gamma, const float* beta, float* y, double* sums, int sums_stride,
+                           const int64_t* frames, int num_streams, int C, int n_cap, int ldt, float eps, const int32_t* slots, const int32_t* offs,
+                           sep_stream_t stream);
+int sep_online_depthwise_fwd_rag(const float* x, const float* w, const float* bias, float* ring, int64_t ring_stride, float* y, int num_streams,
+                                 int C, int n_cap, int ldt, int P, int dilation, const int32_t* slots, const int32_t* offs, sep_stream_t stream);
+int sep_online_decoder_fwd_rag(const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out, int num_streams,
+                               int n_src, int N, int L, int S, int n_cap, int ldt, const int32_t* slots, const int32_t* offs, sep_stream_t stream);
+int sep_online_advance_rag(int64_t* frames, float* carry, const float* carry_next, int carry_len, float* tail, const float* tail_next, int tail_len,
+                           int num_streams, int n_cap, const int32_t* slots, const int32_t* offs, sep_stream_t stream);
 
 /* ---- the causal TCN layer's first norm folded into its depthwise convolution (ABI 23, additive; csrc/causal.hip) ------------------------
  * The first cLN of a causal layer (tdcn.py:107-147) feeds only the depthwise convolution, so its output v1 need not exist in memory:

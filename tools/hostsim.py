@@ -183,6 +183,18 @@ with hostsim.HostSimBackend({so!r}) as K:
             t0 = time.time()
             getattr(SG, name)(*p)
             print("  online {{:27s}} {{:28s}} {{:5.1f}} s".format(name, str(p)[:28], time.time() - t0), flush=True)
+    import test_online_ragged_gpu as RG                                            # ... with a length per stream (the _rag entry points)
+    for name, params in RG.CASES:
+        if only and not any(o in "online_" + name for o in only):
+            continue
+        for p in params:
+            t0 = time.time()
+            getattr(RG, name)(*p)
+            print("  online {{:27s}} {{:28s}} {{:5.1f}} s".format(name, str(p)[:28], time.time() - t0), flush=True)
+    if not only or any(o in "online_equal_lengths" for o in only):
+        t0 = time.time()
+        RG.check_equal_lengths_are_the_sel_call()
+        print("  online {{:27s}} {{:28s}} {{:5.1f}} s".format("equal_lengths_rag_vs_sel", "", time.time() - t0), flush=True)
     import test_causal_recorded_gpu as CG                                          # the folded causal entry points' cases (csrc/causal.hip, sep_cln_stats)
     CG.HIP, CG.to_device, CG.device_sync, CG.device_name = K, (lambda t: t.clone()), (lambda: None), (lambda: "cpu")
     for name, params in CG.CASES:
@@ -247,7 +259,7 @@ def run_case(argv):
 
 def main():
     """python tools/hostsim.py --asan | --tsan [--only NAMES] : the kernel cases of the CPU tier once more (tests/test_kernel_source_on_host_cpu.py
-    the online cases of tests/test_online_gpu.py and tests/test_online_streams_gpu.py -- `--only online` selects those -- and the folded causal cases of
+    the online cases of tests/test_online_gpu.py, tests/test_online_streams_gpu.py and tests/test_online_ragged_gpu.py -- `--only online` selects those -- and the folded causal cases of
     tests/test_causal_recorded_gpu.py -- `--only causal`), with the kernel sources compiled under a
     sanitizer.  --asan: out-of-bounds reads / writes of global buffers (torch's allocations go through the intercepted allocator) and of
     the workgroup's LDS (function-local statics here) that happen to be harmless on the device.  --tsan: data races on LDS or global
