@@ -14,6 +14,14 @@
 //
 // sep_cln_stats itself lives in cln.hip: it is sep_cln_fwd's own kernels without the apply pass (one source, bit-identical statistics).
 //
+// Also here: sep_unfold_dilated / sep_fold_dilated, the dilated unfold (im2col over the taps) of a (B, C, ldt) activation and its adjoint, for
+// the causal layers with FULL k-tap convolutions (separable=False: reference src/models/tdcn.py:100-147).  With the unfolded row index
+// c * P + p a layer's nn.Conv1d(H, M, P, dilation=d) weight (M, H, P) is, in place, the (M, H P) matrix of a 1x1 product over the unfolded
+// rows, so the two convolutions of a layer, their input gradient and their weight gradients are the products the separable layers run.
+// Streaming kernels: a lane owns four consecutive frames of a row, reads them for every tap as one or two aligned 16-byte loads (the
+// tap's shift modulo four is uniform over the launch, so the pick of four out of eight is a uniform switch), masks with selects (what
+// lies beyond T may be NaN) and stores 16 bytes.  One writer per output element, no atomics.
+//
 // One (b, c) row per workgroup, as the depthwise row kernels of stream.hip: the normalised row is formed ONCE into LDS (float4 loads of
 // a, mean, rstd), the taps then read LDS -- float4 where every tap shift is a multiple of four frames (d % 4 == 0), one frame per lane
 // (conflict-free) otherwise.  Any kernel width, any dilation >= 1, 0 <= pad <= (Kw - 1) d; three taps are unrolled.  Rows that do not
@@ -179,6 +187,58 @@ __global__ __launch_bounds__(256) void cd_sum_f64_kernel(const float* __restrict
     if (threadIdx.x == 0) out[0] = (float)tot;
 }
 
+// frames [i, i + 4) of a row of ldt floats (ldt % 4 == 0), i of any sign and alignment, as aligned 16-byte loads; r = i & 3 is uniform over
+// the launch.  Quads that are not wholly inside [0, ldt) read as zero: their frames are outside [0, T) and masked by the caller anyway.
+__device__ __forceinline__ float4 ud_quad(const float* __restrict__ row, const int q, const int ldt) {
+    return (q >= 0 && q + 4 <= ldt) ? cd_ld4(row + q) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+__device__ __forceinline__ float4 ud_window(const float* __restrict__ row, const int i, const int ldt) {
+    const int r = i & 3, q = i - r;
+    const float4 a = ud_quad(row, q, ldt);
+    if (r == 0) return a;
+    const float4 b = ud_quad(row, q + 4, ldt);
+    if (r == 1) return make_float4(a.y, a.z, a.w, b.x);
+    if (r == 2) return make_float4(a.z, a.w, b.x, b.y);
+    return make_float4(a.w, b.x, b.y, b.z);
+}
+// the four frames kept where both the destination frame t + e and the source frame i + e lie in [0, T), zero elsewhere (selects: no NaN passes)
+__device__ __forceinline__ float4 ud_mask(const float4 v, const int t, const int i, const int T) {
+    float4 o;
+    o.x = (t < T && i >= 0 && i < T) ? v.x : 0.f;
+    o.y = (t + 1 < T && i + 1 >= 0 && i + 1 < T) ? v.y : 0.f;
+    o.z = (t + 2 < T && i + 2 >= 0 && i + 2 < T) ? v.z : 0.f;
+    o.w = (t + 3 < T && i + 3 >= 0 && i + 3 < T) ? v.w : 0.f;
+    return o;
+}
+
+// cols[row P + p][t] = x[row][t + p dil - pad] where both frames are in [0, T), zero elsewhere (all of [T, ldt) included).  grid (rows, frame tiles of 1024)
+__global__ __launch_bounds__(256) void ud_unfold_kernel(const float* __restrict__ x, float* __restrict__ cols, int T, int ldt, int P, int dil, int pad) {
+    const int64_t row = blockIdx.x;
+    const int t = 4 * (blockIdx.y * 256 + threadIdx.x);
+    if (t >= ldt) return;
+    const float* xr = x + (size_t)row * ldt;
+    float* cr = cols + (size_t)row * P * ldt + t;
+    for (int p = 0; p < P; ++p) {
+        const int i = t + p * dil - pad;
+        cd_st4(cr + (size_t)p * ldt, ud_mask(ud_window(xr, i, ldt), t, i, T));
+    }
+}
+
+// dx[row][u] = sum_p dcols[row P + p][u - p dil + pad] over the p whose frame is in [0, T), ascending p; zero for u >= T
+__global__ __launch_bounds__(256) void ud_fold_kernel(const float* __restrict__ dcols, float* __restrict__ dx, int T, int ldt, int P, int dil, int pad) {
+    const int64_t row = blockIdx.x;
+    const int u = 4 * (blockIdx.y * 256 + threadIdx.x);
+    if (u >= ldt) return;
+    const float* cr = dcols + (size_t)row * P * ldt;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int p = 0; p < P; ++p) {
+        const int i = u - p * dil + pad;
+        const float4 v = ud_mask(ud_window(cr + (size_t)p * ldt, i, ldt), u, i, T);
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    }
+    cd_st4(dx + (size_t)row * ldt + u, acc);
+}
+
 inline bool cd_args_ok(int B, int C, int T, int ldt, int Kw, int pad, int dil) {
     return B > 0 && C > 0 && T > 0 && ldt >= T && ldt % 4 == 0 && Kw >= 1 && dil >= 1 && pad >= 0 && (long)pad <= (long)(Kw - 1) * dil &&
            (long)B * C <= 0x7fffffffL;
@@ -230,5 +290,24 @@ extern "C" int sep_depthwise_cln_bwd_weight(const float* dy, const float* x, con
     }
 #undef SEP_CDW
     SEP_CHECK_LAUNCH("sep_depthwise_cln_bwd_weight");
+    return 0;
+}
+
+/* the dilated unfold of the causal layers with full k-tap convolutions and its adjoint (include/sepkernels.h) */
+extern "C" int sep_unfold_dilated(const float* x, float* cols, int B, int C, int T, int ldt, int P, int dil, int pad, sep_stream_t stream) {
+    SEP_REQUIRE(x && cols && x != cols && cd_args_ok(B, C, T, ldt, P, pad, dil) && (long)(P - 1) * dil <= 0x3fffffffL,
+                "sep_unfold_dilated: bad arguments (ldt a multiple of 4, 0 <= pad <= (P - 1) dil)");
+    SEP_REQUIRE(ldt <= 65535 * 1024, "sep_unfold_dilated: ldt = %d exceeds the grid", ldt);
+    hipLaunchKernelGGL(ud_unfold_kernel, dim3((unsigned)((long)B * C), (unsigned)((ldt + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, x, cols, T, ldt, P, dil, pad);
+    SEP_CHECK_LAUNCH("sep_unfold_dilated");
+    return 0;
+}
+
+extern "C" int sep_fold_dilated(const float* dcols, float* dx, int B, int C, int T, int ldt, int P, int dil, int pad, sep_stream_t stream) {
+    SEP_REQUIRE(dcols && dx && dcols != dx && cd_args_ok(B, C, T, ldt, P, pad, dil) && (long)(P - 1) * dil <= 0x3fffffffL,
+                "sep_fold_dilated: bad arguments (ldt a multiple of 4, 0 <= pad <= (P - 1) dil)");
+    SEP_REQUIRE(ldt <= 65535 * 1024, "sep_fold_dilated: ldt = %d exceeds the grid", ldt);
+    hipLaunchKernelGGL(ud_fold_kernel, dim3((unsigned)((long)B * C), (unsigned)((ldt + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, dcols, dx, T, ldt, P, dil, pad);
+    SEP_CHECK_LAUNCH("sep_fold_dilated");
     return 0;
 }

@@ -8,6 +8,7 @@
 //   sep_online_encoder_fwd    analysis convolution of [carry | chunk] (filterbank.py:205-235), new carry -> carry_next
 //   sep_online_cln_fwd        [PReLU ->] cLN with the fp64 running sums {sum x, sum x^2} of every stream carried in device memory
 //   sep_online_depthwise_fwd  causal dilated depthwise taps over [history | chunk], the history of (P - 1) d frames kept in time order
+//   sep_online_unfold_fwd     the same history, no taps: the dilated unfold of [history | chunk] for a layer with full k-tap convolutions
 //   sep_online_decoder_fwd    mask * w, synthesis and overlap-add into [tail | n S]: n S final samples, new tail -> tail_next
 //   sep_online_advance        frame counters += n, carry <- carry_next, tail <- tail_next (the last launch of a chunk)
 //   sep_online_reset          zero the state of the streams a device mask selects
@@ -236,6 +237,46 @@ __global__ __launch_bounds__(256) void online_depthwise_kernel(const float* __re
     }
 }
 
+// The depthwise kernel without its taps, for a layer whose convolutions are full (separable=False): cols[c P + p][f] = ext[f + p d], the
+// dilated unfold of ext = [history | x] over the row index c P + p that makes the layer's (M, C, P) weights the matrix of a 1x1 product.
+// Same ownership: workgroup (channel, block) copies the history to LDS before the barrier, writes its P rows of cols and the new history
+// after it.  History layout, ring_stride, slot list and offs are the depthwise kernel's.
+template <bool SEL, bool RAG>
+__global__ __launch_bounds__(256) void online_unfold_kernel(const float* __restrict__ x, float* __restrict__ ring, int64_t ring_stride, float* __restrict__ cols,
+                                                            int n, int ldt, int P, int d, const int32_t* __restrict__ slots, const int32_t* __restrict__ offs) {
+    extern __shared__ float hist[];
+    const int c = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
+    const int D = (P - 1) * d;
+    float* rg = ring + (size_t)slot_of<SEL>(slots, s) * ring_stride + (size_t)c * D;
+    size_t col0 = (size_t)s * n;
+    if constexpr (RAG) {
+        col0 = (size_t)offs[s];
+        n = offs[s + 1] - offs[s];
+    }
+    const float* xr = x + (size_t)c * ldt + col0;
+    float* cr = cols + (size_t)c * P * ldt + col0;
+    for (int i = tid; i < D; i += 256) hist[i] = rg[i];
+    __syncthreads();
+    for (int g = tid; g < P * n; g += 256) {
+        const int p = g / n, f = g - p * n;
+        const int e = f + p * d;
+        cr[(size_t)p * ldt + f] = e < D ? hist[e] : xr[e - D];
+    }
+    for (int i = tid; i < D; i += 256) {
+        const int e = n + i;
+        rg[i] = e < D ? hist[e] : xr[e - D];
+    }
+    if (s == (int)gridDim.y - 1) {
+        int used = (int)gridDim.y * n;
+        if constexpr (RAG) used = offs[gridDim.y];
+        const int pad = ldt - used;
+        for (int g = tid; g < P * pad; g += 256) {
+            const int p = g / pad, j = g - p * pad;
+            cols[((size_t)c * P + p) * ldt + used + j] = 0.f;
+        }
+    }
+}
+
 // Thread per output sample i of [0, n S + L - S) of (stream, source): the old tail plus the overlap-add of the frames that cover i
 // (f S <= i < f S + L), latent = w * mask.  i < n S goes to out, the rest to tail_next.  RAG: the grid covers n_cap S + L - S samples, the stream has
 // n_s frames at columns offs[s] ..; its row of out has the pitch n_cap S and is written as zero from n_s S on.
@@ -366,6 +407,22 @@ static int online_depthwise(const char* who, const float* x, const float* w, con
     return 0;
 }
 
+static int online_unfold(const char* who, const float* x, float* ring, int64_t ring_stride, float* cols, int num_streams, int C, int n, int ldt, int P,
+                         int dilation, const int32_t* slots, const int32_t* offs, sep_stream_t stream) {
+    SEP_REQUIRE(x && cols && x != cols && num_streams > 0 && num_streams <= 65535 && C > 0 && n > 0 && P >= 1 && dilation > 0, "%s: bad arguments", who);
+    const int64_t D = (int64_t)(P - 1) * dilation;
+    SEP_REQUIRE(D <= 16384, "%s: history of %lld frames exceeds LDS", who, (long long)D);
+    SEP_REQUIRE(ring || D == 0, "%s: ring missing", who);
+    SEP_REQUIRE(ring_stride >= (int64_t)C * D, "%s: ring_stride %lld < C (P - 1) d", who, (long long)ring_stride);
+    SEP_REQUIRE((int64_t)num_streams * (offs ? 1 : n) <= ldt && ldt % 128 == 0 && (int64_t)P * ldt <= 0x7fffffff, "%s: bad sizes (streams=%d n=%d ldt=%d P=%d)",
+                who, num_streams, n, ldt, P);
+    const auto kern = offs ? online_unfold_kernel<true, true> : slots ? online_unfold_kernel<true, false> : online_unfold_kernel<false, false>;
+    hipLaunchKernelGGL(kern, dim3(C, num_streams), dim3(256), (size_t)D * sizeof(float), (hipStream_t)stream, x, ring, ring_stride, cols, n, ldt, P,
+                       dilation, slots, offs);
+    SEP_CHECK_LAUNCH(who);
+    return 0;
+}
+
 static int online_decoder(const char* who, const float* w, const float* mask, const float* D, const float* tail, float* tail_next, float* out,
                           int num_streams, int n_src, int N, int L, int S, int n, int ldt, const int32_t* slots, const int32_t* offs,
                           sep_stream_t stream) {
@@ -485,6 +542,23 @@ extern "C" int sep_online_advance_rag(int64_t* frames, float* carry, const float
     SEP_REQUIRE(slots && offs, "sep_online_advance_rag: slots / offs missing");
     return online_advance("sep_online_advance_rag", frames, carry, carry_next, carry_len, tail, tail_next, tail_len, num_streams, n_cap, slots, offs,
                           stream);
+}
+
+extern "C" int sep_online_unfold_fwd(const float* x, float* ring, int64_t ring_stride, float* cols, int num_streams, int C, int n, int ldt, int P,
+                                     int dilation, sep_stream_t stream) {
+    return online_unfold("sep_online_unfold_fwd", x, ring, ring_stride, cols, num_streams, C, n, ldt, P, dilation, nullptr, nullptr, stream);
+}
+
+extern "C" int sep_online_unfold_fwd_sel(const float* x, float* ring, int64_t ring_stride, float* cols, int num_streams, int C, int n, int ldt, int P,
+                                         int dilation, const int32_t* slots, sep_stream_t stream) {
+    SEP_REQUIRE(slots, "sep_online_unfold_fwd_sel: slots missing");
+    return online_unfold("sep_online_unfold_fwd_sel", x, ring, ring_stride, cols, num_streams, C, n, ldt, P, dilation, slots, nullptr, stream);
+}
+
+extern "C" int sep_online_unfold_fwd_rag(const float* x, float* ring, int64_t ring_stride, float* cols, int num_streams, int C, int n_cap, int ldt, int P,
+                                         int dilation, const int32_t* slots, const int32_t* offs, sep_stream_t stream) {
+    SEP_REQUIRE(slots && offs, "sep_online_unfold_fwd_rag: slots / offs missing");
+    return online_unfold("sep_online_unfold_fwd_rag", x, ring, ring_stride, cols, num_streams, C, n_cap, ldt, P, dilation, slots, offs, stream);
 }
 
 extern "C" int sep_online_reset(const uint8_t* mask, int num_streams, int64_t* frames, float* carry, int carry_len, double* sums, int sums_len,

@@ -68,6 +68,7 @@ const seq_entry SEQ_TABLE[] = {
     SEQ_FN(sep_online_encoder_fwd_rag), SEQ_FN(sep_online_cln_fwd_rag), SEQ_FN(sep_online_depthwise_fwd_rag), SEQ_FN(sep_online_decoder_fwd_rag),
     SEQ_FN(sep_online_advance_rag),
     SEQ_FN(sep_cln_stats), SEQ_FN(sep_depthwise_cln_fwd), SEQ_FN(sep_depthwise_cln_bwd_weight), SEQ_FN(sep_sum_f64),
+    SEQ_FN(sep_unfold_dilated), SEQ_FN(sep_fold_dilated), SEQ_FN(sep_online_unfold_fwd), SEQ_FN(sep_online_unfold_fwd_sel), SEQ_FN(sep_online_unfold_fwd_rag),
 };
 constexpr int SEQ_COUNT = (int)(sizeof(SEQ_TABLE) / sizeof(SEQ_TABLE[0]));
 

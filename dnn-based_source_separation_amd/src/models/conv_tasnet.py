@@ -83,19 +83,19 @@ class _FusedConvTasNetFn(torch.autograd.Function):
 
 def _layout(named_sizes):
     """Offsets (in floats) of every parameter inside the flat buffer.  Every tensor starts 16-byte aligned; for each
-    TCN layer the pair (output_pointwise.weight, skip_pointwise.weight) and the pair of their biases are adjacent."""
+    TCN layer the pair (output_pointwise.weight, skip_pointwise.weight) and the pair of their biases are adjacent -- and so are
+    (output_conv1d.weight, skip_conv1d.weight) and their biases in a layer without separable convolutions."""
     sizes = dict(named_sizes)
     order, seen = [], set()
     for n, _ in named_sizes:
         if n in seen:
             continue
-        if n.endswith("output_pointwise_conv1d.weight"):
-            base = n[:-len("output_pointwise_conv1d.weight")]
-            group = [base + "output_pointwise_conv1d.weight", base + "skip_pointwise_conv1d.weight",
-                     base + "output_pointwise_conv1d.bias", base + "skip_pointwise_conv1d.bias"]
-            group = [g for g in group if g in sizes]
-        else:
-            group = [n]
+        group = [n]
+        for out, skip in (("output_pointwise_conv1d.", "skip_pointwise_conv1d."), ("output_conv1d.", "skip_conv1d.")):
+            if n.endswith("." + out + "weight"):
+                base = n[:-len(out + "weight")]
+                group = [base + out + "weight", base + skip + "weight", base + out + "bias", base + skip + "bias"]
+                group = [g for g in group if g in sizes]
         for g in group:
             if g not in seen:
                 order.append(g)
@@ -396,8 +396,8 @@ class ConvTasNet(nn.Module):
             problems.append("enc_basis/dec_basis must be 'trainable'")
         if cfg.get("enc_nonlinear") not in (None, "", "relu"):
             problems.append("enc_nonlinear must be None or 'relu'")
-        if not cfg.get("separable", True) or not cfg.get("dilated", True):
-            problems.append("separable=True and dilated=True are required")
+        if not cfg.get("dilated", True) or (not cfg.get("separable", True) and not cfg.get("causal")):
+            problems.append("separable=True and dilated=True are required")        # (separable=False: the causal family only, below)
         if cfg.get("sep_nonlinear") != "prelu" or not cfg.get("sep_norm", True):
             problems.append("sep_nonlinear='prelu' and sep_norm=True are required")
         for k in ("n_basis", "sep_hidden_channels", "sep_bottleneck_channels", "sep_skip_channels"):
@@ -414,8 +414,11 @@ class ConvTasNet(nn.Module):
             cLN, 1x1 bottleneck              PaddedCLNFn, PaddedPointwiseFn   sep_cln_*, sep_pw_gemm
             per layer  1x1 -> PReLU+cLN -> depthwise (left padding (P-1) d) -> PReLU+cLN -> [1x1 output + residual ; 1x1 skip, summed]
                                              PaddedPointwiseFn, PaddedCLNDepthwiseFn, PaddedCLNFn, PaddedHeadsFn
+            separable=False (tdcn.py:100-104, 133-147): 1x1 -> PReLU+cLN -> dilated unfold over the taps (left padding (P-1) d) -> the two
+            P-tap convolutions as the heads' products over the unfolded rows, K = H P
+                                             PaddedPointwiseFn, PaddedCLNFn, PaddedUnfoldFn, PaddedHeadsFn
             PReLU + 1x1 mask, sigmoid | softmax, mask * w -> decoder -> crop     TailFn (net.tail_forward / tail_backward)"""
-        from sepkernels.functional import EncodeFn, PaddedPointwiseFn, PaddedCLNFn, PaddedCLNDepthwiseFn, PaddedHeadsFn, TailFn
+        from sepkernels.functional import EncodeFn, PaddedPointwiseFn, PaddedCLNFn, PaddedCLNDepthwiseFn, PaddedHeadsFn, PaddedUnfoldFn, TailFn
         B, Cin, T = mixture.shape
         sep = self.separator
         geo = _net.Geometry(T, self.kernel_size, self.stride)
@@ -427,9 +430,17 @@ class ConvTasNet(nn.Module):
         total = None
         for block in sep.tdcn.net:
             for layer in block.net:
-                dw = layer.separable_conv1d
                 d, P = layer.dilation, layer.kernel_size
                 a = PaddedPointwiseFn.apply(x, F_, layer.bottleneck_conv1d.weight, layer.bottleneck_conv1d.bias, None, wa)
+                if not layer.separable:
+                    # one norm, then the two full convolutions: rows c P + p of the unfolded tensor against the (M, H, P) weights as they lie
+                    v = PaddedCLNFn.apply(a, F_, layer.nonlinear1d.weight, layer.norm1d.gamma, layer.norm1d.beta, layer.norm1d.eps)
+                    cols = PaddedUnfoldFn.apply(v, F_, P, d, (P - 1) * d)
+                    out = layer.output_conv1d if layer.dual_head else None
+                    x, total = PaddedHeadsFn.apply(cols, F_, out.weight if out is not None else None, out.bias if out is not None else None,
+                                                   layer.skip_conv1d.weight, layer.skip_conv1d.bias, x, total, wa)
+                    continue
+                dw = layer.separable_conv1d
                 # first norm + depthwise taps as one node: with the folded kernels (sep_cln_stats, sep_depthwise_cln_*) the normalised tensor
                 # is formed on load and never written; otherwise the sep_cln_fwd / sep_depthwise_fwd pair (sepkernels.functional.cln_depthwise_forward)
                 z = PaddedCLNDepthwiseFn.apply(a, F_, layer.nonlinear1d.weight, layer.norm1d.gamma, layer.norm1d.beta, layer.norm1d.eps,

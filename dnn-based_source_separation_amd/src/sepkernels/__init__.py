@@ -221,6 +221,12 @@ SIGNATURES = {
     "sep_depthwise_cln_fwd": [_vp] * 9 + [_I] * 7 + [_vp],
     "sep_depthwise_cln_bwd_weight": [_vp] * 8 + [_I] * 7 + [_vp],
     "sep_sum_f64": [_vp, _L, _vp, _vp],
+    # the causal layer with full k-tap convolutions: dilated unfold over the taps, its adjoint, the online form (ABI 23, additive)
+    "sep_unfold_dilated": [_vp, _vp] + [_I] * 7 + [_vp],
+    "sep_fold_dilated": [_vp, _vp] + [_I] * 7 + [_vp],
+    "sep_online_unfold_fwd": [_vp, _vp, _L, _vp] + [_I] * 6 + [_vp],
+    "sep_online_unfold_fwd_sel": [_vp, _vp, _L, _vp] + [_I] * 6 + [_vp, _vp],
+    "sep_online_unfold_fwd_rag": [_vp, _vp, _L, _vp] + [_I] * 6 + [_vp, _vp, _vp],
 }
 _RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_last_kernel": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
              "sep_gln_tokens_ws_bytes": ctypes.c_size_t}
@@ -604,6 +610,12 @@ class HipBackend:
                                                    _ptr(rstd, _f32), _ptr(partial, _f32), B, C, T, ldt, Kw, pad, dil, _stream()),
                "sep_depthwise_cln_bwd_weight")
 
+    def unfold_dilated(self, x, cols, B, C, T, ldt, P, dil, pad):
+        _check(load().sep_unfold_dilated(_ptr(x, _f32), _ptr(cols, _f32), B, C, T, ldt, P, dil, pad, _stream()), "sep_unfold_dilated")
+
+    def fold_dilated(self, dcols, dx, B, C, T, ldt, P, dil, pad):
+        _check(load().sep_fold_dilated(_ptr(dcols, _f32), _ptr(dx, _f32), B, C, T, ldt, P, dil, pad, _stream()), "sep_fold_dilated")
+
     def attn_fwd(self, qkv, o, lse, N, L, H, D, scale, p_drop=0.0, seed=0):
         _check(load().sep_attn_fwd(_ptr(qkv, _f32), _ptr(o, _f32), _ptr(lse, _f32), N, L, H, D, scale, p_drop, seed, _stream()), "sep_attn_fwd")
 
@@ -780,6 +792,10 @@ class HipBackend:
         _check(load().sep_online_depthwise_fwd(_ptr(x, _f32), _ptr(w, _f32), _ptr(bias, _f32), _ptr(ring, _f32), ring_stride, _ptr(y, _f32),
                                                num_streams, C, n, ldt, P, dilation, _stream()), "sep_online_depthwise_fwd")
 
+    def online_unfold_fwd(self, x, ring, ring_stride, cols, num_streams, C, n, ldt, P, dilation):
+        _check(load().sep_online_unfold_fwd(_ptr(x, _f32), _ptr(ring, _f32), ring_stride, _ptr(cols, _f32), num_streams, C, n, ldt, P, dilation,
+                                            _stream()), "sep_online_unfold_fwd")
+
     def online_decoder_fwd(self, w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n, ldt):
         _check(load().sep_online_decoder_fwd(_ptr(w, _f32), _ptr(mask, _f32), _ptr(D, _f32), _ptr(tail, _f32), _ptr(tail_next, _f32), _ptr(out, _f32),
                                              num_streams, n_src, N, L, S, n, ldt, _stream()), "sep_online_decoder_fwd")
@@ -808,6 +824,10 @@ class HipBackend:
                                                    num_streams, C, n, ldt, P, dilation, _ptr(slots, torch.int32), _stream()),
                "sep_online_depthwise_fwd_sel")
 
+    def online_unfold_fwd_sel(self, x, ring, ring_stride, cols, num_streams, C, n, ldt, P, dilation, slots):
+        _check(load().sep_online_unfold_fwd_sel(_ptr(x, _f32), _ptr(ring, _f32), ring_stride, _ptr(cols, _f32), num_streams, C, n, ldt, P, dilation,
+                                                _ptr(slots, torch.int32), _stream()), "sep_online_unfold_fwd_sel")
+
     def online_decoder_fwd_sel(self, w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n, ldt, slots):
         _check(load().sep_online_decoder_fwd_sel(_ptr(w, _f32), _ptr(mask, _f32), _ptr(D, _f32), _ptr(tail, _f32), _ptr(tail_next, _f32),
                                                  _ptr(out, _f32), num_streams, n_src, N, L, S, n, ldt, _ptr(slots, torch.int32), _stream()),
@@ -834,6 +854,10 @@ class HipBackend:
         _check(load().sep_online_depthwise_fwd_rag(_ptr(x, _f32), _ptr(w, _f32), _ptr(bias, _f32), _ptr(ring, _f32), ring_stride, _ptr(y, _f32),
                                                    num_streams, C, n_cap, ldt, P, dilation, _ptr(slots, torch.int32), _ptr(offs, torch.int32),
                                                    _stream()), "sep_online_depthwise_fwd_rag")
+
+    def online_unfold_fwd_rag(self, x, ring, ring_stride, cols, num_streams, C, n_cap, ldt, P, dilation, slots, offs):
+        _check(load().sep_online_unfold_fwd_rag(_ptr(x, _f32), _ptr(ring, _f32), ring_stride, _ptr(cols, _f32), num_streams, C, n_cap, ldt, P, dilation,
+                                                _ptr(slots, torch.int32), _ptr(offs, torch.int32), _stream()), "sep_online_unfold_fwd_rag")
 
     def online_decoder_fwd_rag(self, w, mask, D, tail, tail_next, out, num_streams, n_src, N, L, S, n_cap, ldt, slots, offs):
         _check(load().sep_online_decoder_fwd_rag(_ptr(w, _f32), _ptr(mask, _f32), _ptr(D, _f32), _ptr(tail, _f32), _ptr(tail_next, _f32),

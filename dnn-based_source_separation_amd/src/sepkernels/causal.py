@@ -14,6 +14,9 @@ Against _run_staged + autograd's backward of it, launch for launch, the differen
     PReLU slopes: pa.sum(dtype=float64)           sep_sum_f64 (fp64 accumulation in a fixed order)
     depthwise d weight / d bias slices            two sep_repack copies of the summed (C, Kw + 1) rows
     torch.zeros                                   K.zeros / sep_memset
+A model with separable=False (full P-tap convolutions output_conv1d / skip_conv1d, reference tdcn.py:100-104, 133-147) takes the second branch of
+the layer loops: conv1 -> PReLU + cLN -> sep_unfold_dilated -> the heads' products over the unfolded rows (K = H P, the (M, H, P) weights as they
+lie), and backward the [Wo; Ws]^T product, sep_fold_dilated and the one norm's backward -- the same entry points, so the step records alike.
 reference: src/models/conv_tasnet.py:121-171, tdcn.py:107-147 / 177-196, modules/norm.py:58-101.
 """
 import torch
@@ -70,9 +73,19 @@ def _forward(cfg, P, mixture, want_latent, save):
 
     total = None
     acts = []
+    dense = not cfg.get("separable", True)
     for pre, dil, dual in _net.layer_names(cfg):
         sp = pre + "separable_conv1d."
         a = _fn.pointwise_forward(x, F, P[pre + "bottleneck_conv1d.weight"], P[pre + "bottleneck_conv1d.bias"], None)
+        if dense:
+            v, mean1, rstd1 = _fn.cln_forward(a, F, P[pre + "nonlinear1d.weight"], _flat(P[pre + "norm1d.gamma"]), _flat(P[pre + "norm1d.beta"]), teps)
+            cols = _fn.unfold_forward(v, F, Pk, dil, (Pk - 1) * dil)
+            xo, total = _fn.heads_forward(cols, F, P[pre + "output_conv1d.weight"] if dual else None, P[pre + "output_conv1d.bias"] if dual else None,
+                                          P[pre + "skip_conv1d.weight"], P[pre + "skip_conv1d.bias"], x, total)
+            if save:
+                acts.append((x, a, mean1, rstd1, cols))
+            x = xo
+            continue
         z, sv1 = _fn.cln_depthwise_forward(a, F, P[pre + "nonlinear1d.weight"], _flat(P[pre + "norm1d.gamma"]), _flat(P[pre + "norm1d.beta"]), teps,
                                            P[sp + "depthwise_conv1d.weight"], P[sp + "depthwise_conv1d.bias"], dil, (Pk - 1) * dil)
         v2, mean2, rstd2 = _fn.cln_forward(z, F, P[sp + "nonlinear1d.weight"], _flat(P[sp + "norm1d.gamma"]), _flat(P[sp + "norm1d.beta"]), teps)
@@ -118,6 +131,7 @@ def _backward(cfg, P, sv, d_est, G, on_ready=None):
     f32 = dict(device=mixture.device, dtype=mixture.dtype)
     layers = _net.layer_names(cfg)
     X_layers = cfg["sep_num_layers"]
+    dense = not cfg.get("separable", True)
 
     # tail: decoder, mask * w, mask nonlinearity, mask convolution behind its PReLU
     dal = _net._zeros(K, 1, device=mixture.device, dtype=torch.float64)
@@ -130,17 +144,27 @@ def _backward(cfg, P, sv, d_est, G, on_ready=None):
     for li in range(len(layers) - 1, -1, -1):
         pre, dil, dual = layers[li]
         sp = pre + "separable_conv1d."
-        x, a, sv1, z, mean2, rstd2, v2 = sv.acts[li]
-        dv2 = _fn.heads_backward(v2, P[sp + "output_pointwise_conv1d.weight"] if dual else None, P[sp + "skip_pointwise_conv1d.weight"], None, F,
-                                 d_out if dual else None, dS,
-                                 dWo=G[sp + "output_pointwise_conv1d.weight"] if dual else None, dbo=G[sp + "output_pointwise_conv1d.bias"] if dual else None,
-                                 dWs=G[sp + "skip_pointwise_conv1d.weight"], dbs=G[sp + "skip_pointwise_conv1d.bias"])[0]
-        dz = _fn.cln_backward(dv2, z, _flat(P[sp + "norm1d.gamma"]), mean2, rstd2, P[sp + "nonlinear1d.weight"], F, teps,
-                              dgamma=_flat(G[sp + "norm1d.gamma"]), dbeta=_flat(G[sp + "norm1d.beta"]), dalpha=G[sp + "nonlinear1d.weight"])[0]
-        da = _fn.cln_depthwise_backward(dz, a, sv1, P[pre + "nonlinear1d.weight"], _flat(P[pre + "norm1d.gamma"]), _flat(P[pre + "norm1d.beta"]), teps, F,
-                                        P[sp + "depthwise_conv1d.weight"], dil, (Pk - 1) * dil, True,
-                                        dweight=G[sp + "depthwise_conv1d.weight"], dbias=G[sp + "depthwise_conv1d.bias"],
-                                        dgamma=_flat(G[pre + "norm1d.gamma"]), dbeta=_flat(G[pre + "norm1d.beta"]), dalpha=G[pre + "nonlinear1d.weight"])[0]
+        if dense:
+            x, a, mean1, rstd1, cols = sv.acts[li]
+            dcols = _fn.heads_backward(cols, P[pre + "output_conv1d.weight"] if dual else None, P[pre + "skip_conv1d.weight"], None, F,
+                                       d_out if dual else None, dS,
+                                       dWo=G[pre + "output_conv1d.weight"] if dual else None, dbo=G[pre + "output_conv1d.bias"] if dual else None,
+                                       dWs=G[pre + "skip_conv1d.weight"], dbs=G[pre + "skip_conv1d.bias"])[0]
+            dv = _fn.unfold_backward(dcols, F, Pk, dil, (Pk - 1) * dil)
+            da = _fn.cln_backward(dv, a, _flat(P[pre + "norm1d.gamma"]), mean1, rstd1, P[pre + "nonlinear1d.weight"], F, teps,
+                                  dgamma=_flat(G[pre + "norm1d.gamma"]), dbeta=_flat(G[pre + "norm1d.beta"]), dalpha=G[pre + "nonlinear1d.weight"])[0]
+        else:
+            x, a, sv1, z, mean2, rstd2, v2 = sv.acts[li]
+            dv2 = _fn.heads_backward(v2, P[sp + "output_pointwise_conv1d.weight"] if dual else None, P[sp + "skip_pointwise_conv1d.weight"], None, F,
+                                     d_out if dual else None, dS,
+                                     dWo=G[sp + "output_pointwise_conv1d.weight"] if dual else None, dbo=G[sp + "output_pointwise_conv1d.bias"] if dual else None,
+                                     dWs=G[sp + "skip_pointwise_conv1d.weight"], dbs=G[sp + "skip_pointwise_conv1d.bias"])[0]
+            dz = _fn.cln_backward(dv2, z, _flat(P[sp + "norm1d.gamma"]), mean2, rstd2, P[sp + "nonlinear1d.weight"], F, teps,
+                                  dgamma=_flat(G[sp + "norm1d.gamma"]), dbeta=_flat(G[sp + "norm1d.beta"]), dalpha=G[sp + "nonlinear1d.weight"])[0]
+            da = _fn.cln_depthwise_backward(dz, a, sv1, P[pre + "nonlinear1d.weight"], _flat(P[pre + "norm1d.gamma"]), _flat(P[pre + "norm1d.beta"]), teps, F,
+                                            P[sp + "depthwise_conv1d.weight"], dil, (Pk - 1) * dil, True,
+                                            dweight=G[sp + "depthwise_conv1d.weight"], dbias=G[sp + "depthwise_conv1d.bias"],
+                                            dgamma=_flat(G[pre + "norm1d.gamma"]), dbeta=_flat(G[pre + "norm1d.beta"]), dalpha=G[pre + "nonlinear1d.weight"])[0]
         dx = _fn.pointwise_backward(x, P[pre + "bottleneck_conv1d.weight"], None, None, F, True, da,
                                     dW=G[pre + "bottleneck_conv1d.weight"], db=G[pre + "bottleneck_conv1d.bias"])[0]
         if dual:

@@ -301,12 +301,22 @@ class PaddedCLNFn(torch.autograd.Function):
         return dx, None, dalpha, dgamma.view(gshape), dbeta.view(bshape), None
 
 
+def _heads_widths(v, Wo, Ws):
+    """-> contraction length, Bn, Sc of a layer's heads.  The weights are (M, H, 1) of the 1x1 heads against v (B, H, ldt), or (M, H, P) of two
+    full P-tap convolutions against the unfolded v (B, H P, ldt) with rows c P + p (unfold_forward): either way a row-major (M, K) matrix with
+    K = v.shape[1], in place."""
+    Kc = v.shape[1]
+    for W in (Wo, Ws):
+        if W is not None and (W.numel() != W.shape[0] * Kc or not W.is_contiguous()):
+            raise ValueError("heads: a weight of shape {} is not an (M, {}) matrix over the {} rows of the input".format(tuple(W.shape), Kc, Kc))
+    return Kc, (Wo.shape[0] if Wo is not None else 0), Ws.shape[0]
+
+
 def heads_forward(v, n_frames, Wo, bo, Ws, bs, x_res, total, a_amax=None):
     """-> xo (None without the output head), total (created when None, else updated in place)"""
     K = backend()
-    B, H, ldt = v.shape
-    Sc = Ws.shape[0]
-    Bn = Wo.shape[0] if Wo is not None else 0
+    B, _, ldt = v.shape
+    H, Bn, Sc = _heads_widths(v, Wo, Ws)
     f32 = dict(device=v.device, dtype=v.dtype)
     first = total is None
     if first:
@@ -326,10 +336,9 @@ def heads_forward(v, n_frames, Wo, bo, Ws, bs, x_res, total, a_amax=None):
 def heads_backward(v, Wo, Ws, a_amax, n_frames, d_out, d_total, dWo=None, dbo=None, dWs=None, dbs=None):
     """-> dv, dWo, dbo (None without the output head or its gradient), dWs, dbs.  d_total must be given (B, Sc, ldt)."""
     K = backend()
-    B, H, ldt = v.shape
+    B, _, ldt = v.shape
     F = n_frames
-    Sc = Ws.shape[0]
-    Bn = Wo.shape[0] if Wo is not None else 0
+    H, Bn, Sc = _heads_widths(v, Wo, Ws)
     f32 = dict(device=v.device, dtype=v.dtype)
     have_o = Wo is not None and d_out is not None
     dv = torch.empty(B, H, ldt, **f32)
@@ -362,7 +371,9 @@ def heads_backward(v, Wo, Ws, a_amax, n_frames, d_out, d_total, dWo=None, dbo=No
 class PaddedHeadsFn(torch.autograd.Function):
     """The two 1x1 heads of a TCN layer on workspace rows in ONE pass over their input (reference tdcn.py:188-196 + :145-147 + the skip sum
     of :36-41, 70-75): out = Wo v + bo + x_res, total += Ws v + bs.  v (B, H, ldt); x_res (B, Bn, ldt); total (B, Sc, ldt) or None (first
-    layer: created) -- UPDATED IN PLACE and returned; Wo / bo None for a layer without the output head.  With Bn % 128 == 0 and the two
+    layer: created) -- UPDATED IN PLACE and returned; Wo / bo None for a layer without the output head.  The weights are (M, H, 1), or
+    (M, C, k) of two full k-tap convolutions against v = PaddedUnfoldFn's (B, C k, ldt): the same products with the contraction length C k,
+    gradients in the parameters' own shapes.  With Bn % 128 == 0 and the two
     weight matrices adjacent in memory (ConvTasNet's flat parameter buffer keeps them so) it is one product over [Wo; Ws] with the residual
     and the accumulation in its epilogue, and one product [Wo; Ws]^T [d out; d total] backward -- instead of two products, two additions
     forward and two products plus the addition of two H-tensors backward."""
@@ -391,6 +402,43 @@ class PaddedHeadsFn(torch.autograd.Function):
             d_out = d_out.contiguous()
         dv, dWo, dbo, dWs, dbs = heads_backward(v, Wo, Ws, a_amax, F, d_out if have_o else None, d_total)
         return dv, None, dWo, dbo, dWs, dbs, (d_out if have_o else None), (None if first else d_total), None
+
+
+def unfold_forward(x, n_frames, taps, dilation, left):
+    """x (B, C, ldt) -> cols (B, C taps, ldt), cols[b][c taps + p][t] = x[b][c][t + p dilation - left] inside the n_frames valid frames, zero
+    elsewhere (sep_unfold_dilated): the input of a full taps-wide dilated convolution as the input of a 1x1 product"""
+    K = backend()
+    B, C, ldt = x.shape
+    cols = torch.empty(B, C * taps, ldt, device=x.device, dtype=x.dtype)
+    K.unfold_dilated(x, cols, B, C, n_frames, ldt, taps, dilation, left)
+    return cols
+
+
+def unfold_backward(dcols, n_frames, taps, dilation, left):
+    """dcols (B, C taps, ldt) -> dx (B, C, ldt): the adjoint gather (sep_fold_dilated)"""
+    K = backend()
+    B, CP, ldt = dcols.shape
+    C = CP // taps
+    dx = torch.empty(B, C, ldt, device=dcols.device, dtype=dcols.dtype)
+    K.fold_dilated(dcols, dx, B, C, n_frames, ldt, taps, dilation, left)
+    return dx
+
+
+class PaddedUnfoldFn(torch.autograd.Function):
+    """The zero padding and the taps of nn.Conv1d(C, M, k, dilation=d) of a TCN layer without separable convolutions (reference tdcn.py:100-147)
+    on rows that carry the workspace stride: x (B, C, ldt) with n_frames valid frames -> (B, C k, ldt), row c k + p holding x shifted by
+    p d - left (`left` zeros in front: (k - 1) d for a causal layer).  PaddedHeadsFn on the result with the layer's (M, C, k) weights is the
+    pair output_conv1d / skip_conv1d; backward is the adjoint fold."""
+
+    @staticmethod
+    def forward(ctx, x, n_frames, taps, dilation, left):
+        ctx.meta = (n_frames, taps, dilation, left)
+        return unfold_forward(x.contiguous(), n_frames, taps, dilation, left)
+
+    @staticmethod
+    def backward(ctx, dcols):
+        n_frames, taps, dilation, left = ctx.meta
+        return unfold_backward(dcols.contiguous(), n_frames, taps, dilation, left), None, None, None, None
 
 
 def depthwise_forward(x, weight, bias, dilation, left):

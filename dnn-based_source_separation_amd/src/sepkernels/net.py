@@ -42,6 +42,8 @@ class Geometry:
 
 
 def layer_names(cfg):
+    """(parameter prefix, dilation, has an output head) of every TCN layer in order.  The staged causal family names its layers' parameters from
+    the prefix: `separable_conv1d.*` below it, or output_conv1d / skip_conv1d directly when cfg["separable"] is False (sepkernels/causal.py)."""
     out = []
     R, X = cfg["sep_num_blocks"], cfg["sep_num_layers"]
     for r in range(R):

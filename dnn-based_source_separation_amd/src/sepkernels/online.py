@@ -13,7 +13,9 @@ and exactly n S output samples per source; flush() returns the last L - S sample
 
 and the separated version of x[t] is output sample t + L - S (algorithmic delay L - S samples).  It holds because a causal model's mask frame f
 depends on encoder frames <= f only -- cLN is cumulative (reference src/modules/norm.py:42-101), the depthwise taps are left-padded by (P - 1) d
-(src/models/tdcn.py:125-132) -- and output sample tau receives overlap-add from the frames f with f S <= tau < f S + L only.
+(src/models/tdcn.py:125-132) -- and output sample tau receives overlap-add from the frames f with f S <= tau < f S + L only.  The same holds
+for the causal family with separable=False (two full P-tap convolutions per layer, left-padded alike): per layer the pass is conv1, cLN,
+sep_online_unfold_fwd (the depthwise kernel's history, no taps: rows c P + p of an (H P, ldt) buffer), and the heads' products over those rows.
 
 A chunk step is net.py-style orchestration: backend calls only, no autograd and no torch kernel between the launches of a chunk.  Every stream's
 n frames are columns stream * n + frame of one (C, ldt) matrix ("stream-major"), so each 1x1 product of a layer is ONE sep_pw_gemm over all
@@ -89,6 +91,8 @@ class _Workspace:
         self.m = torch.zeros(sep.n_src * N, ldt, **f)
         self.out = torch.zeros(Bs, sep.n_src, n * sep.S, **f)
         self.amax = torch.zeros(1, **f)
+        if sep.dense:                                          # separable=False: the normalised activation unfolded over the taps, rows c P + p
+            self.cols = torch.zeros(H * sep.P, ldt, **f)
 
 
 class _Views:
@@ -110,6 +114,8 @@ class _SubsetWorkspace:
         self.offs = torch.zeros(Bs + 1, device=sep.device, dtype=torch.int32)     # ragged calls: the column block of every stream
         self.amax = torch.zeros(1, **f)
         self.rows = dict(w=sep.N, wn=sep.N, xa=sep.Bn, xb=sep.Bn, ha=sep.H, hb=sep.H, total=sep.Sc, m=sep.n_src * sep.N)
+        if sep.dense:
+            self.rows["cols"] = sep.H * sep.P
         self.store = {k: torch.zeros(C * ldt, **f) for k, C in self.rows.items()}
 
     def views(self, A, ldt=None):
@@ -164,9 +170,11 @@ class OnlineSeparator:
         self.Bn, self.Sc = model.sep_bottleneck_channels, model.sep_skip_channels
         self.H = model.sep_hidden_channels
         self.layers = [layer for block in sep.tdcn.net for layer in block.net]
-        self.n_norms = 1 + 2 * len(self.layers)
+        self.dense = not model.separable                       # full P-tap convolutions: one norm per layer, the taps by the online unfold
+        self.P = model.sep_kernel_size
+        self.n_norms = 1 + (1 if self.dense else 2) * len(self.layers)
         self.ring_offsets, off = [], 0
-        for layer in self.layers:
+        for layer in self.layers:                              # (C, (P - 1) d) per layer: the depthwise input's history, or the unfold's
             self.ring_offsets.append(off)
             off += self.H * (layer.kernel_size - 1) * layer.dilation
         self.ring_len = off
@@ -403,22 +411,24 @@ class OnlineSeparator:
         return T // self.S
 
     def _step(self, ws, n, blocks=None, slots=None, offs=None):
-        """one chunk of n frames of every stream: ~5 launches per TCN layer plus encoder, norm, bottleneck, mask, decoder and advance.
+        """one chunk of n frames of every stream: ~5 launches per TCN layer plus encoder, norm, bottleneck, mask, decoder and advance
+        (separable=False: conv1, cLN, online unfold, heads -- 4 or 5).
         With `slots` (device int32): of the `blocks` streams it names, through the sep_online_*_sel entry points.  With `offs` too (device
         int32, blocks + 1 entries): stream j brings offs[j + 1] - offs[j] <= n frames, through the sep_online_*_rag entry points, and the
         products run over all ws.ldt columns"""
         K = backend()
         model, sep = self.model, self.model.separator
         Bs, L, S, N, H, Bn, Sc, n_src = self.num_streams, self.L, self.S, self.N, self.H, self.Bn, self.Sc, self.n_src
+        taps = "online_unfold_fwd" if self.dense else "online_depthwise_fwd"      # the kernel that keeps a layer's history
         if slots is None:
-            encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd, K.online_cln_fwd, K.online_depthwise_fwd, K.online_decoder_fwd,
+            encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd, K.online_cln_fwd, getattr(K, taps), K.online_decoder_fwd,
                                                                   K.online_advance, ())
         elif offs is None:
-            encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd_sel, K.online_cln_fwd_sel, K.online_depthwise_fwd_sel,
+            encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd_sel, K.online_cln_fwd_sel, getattr(K, taps + "_sel"),
                                                                   K.online_decoder_fwd_sel, K.online_advance_sel, (slots,))
             Bs = blocks
         else:
-            encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd_rag, K.online_cln_fwd_rag, K.online_depthwise_fwd_rag,
+            encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd_rag, K.online_cln_fwd_rag, getattr(K, taps + "_rag"),
                                                                   K.online_decoder_fwd_rag, K.online_advance_rag, (slots, offs))
             Bs = blocks
         T, ldt = (Bs * n if offs is None else ws.ldt), ws.ldt
@@ -441,9 +451,18 @@ class OnlineSeparator:
         x, x_next = ws.xa, ws.xb
         rings = self.rings.view(-1)
         for li, layer in enumerate(self.layers):
-            dw = layer.separable_conv1d
             d, P = layer.dilation, layer.kernel_size
             K.pw_gemm(B=1, M=H, K=Bn, T=T, ldt=ldt, A=layer.bottleneck_conv1d.weight, X=x, Y=ws.ha, bias=layer.bottleneck_conv1d.bias, a_amax=amax)
+            if self.dense:
+                # one norm, the taps unfolded into rows c P + p (history of (P - 1) d frames per channel in the ring), the two full convolutions as heads
+                cln(ws.ha, ws.hb, layer.norm1d, layer.nonlinear1d.weight, 1 + li)
+                depthwise(ws.hb, rings[self.ring_offsets[li]:], self.ring_len, ws.cols, Bs, H, n, ldt, P, d, *sel)
+                out = layer.output_conv1d if layer.dual_head else None
+                self._heads(K, ws.cols, out, layer.skip_conv1d, x, x_next, ws.total, li == 0, T, ldt, amax)
+                if out is not None:
+                    x, x_next = x_next, x
+                continue
+            dw = layer.separable_conv1d
             cln(ws.ha, ws.hb, layer.norm1d, layer.nonlinear1d.weight, 1 + 2 * li)
             depthwise(ws.hb, dw.depthwise_conv1d.weight, dw.depthwise_conv1d.bias, rings[self.ring_offsets[li]:], self.ring_len, ws.ha,
                       Bs, H, n, ldt, P, d, *sel)

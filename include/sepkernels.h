@@ -667,6 +667,31 @@ int sep_depthwise_cln_fwd(const float* x, const float* alpha, const float* gamma
 int sep_depthwise_cln_bwd_weight(const float* dy, const float* x, const float* alpha, const float* gamma, const float* beta, const float* mean,
                                  const float* rstd, float* partial, int B, int C, int T, int ldt, int Kw, int pad, int dil, sep_stream_t stream);
 
+/* ---- the causal TCN layer with full k-tap convolutions (separable=False) on the 1x1 products (ABI 23, additive) ------------------------------
+ * A layer of ConvTasNet(causal=True, separable=False) (reference tdcn.py:100-147) is conv1 -> PReLU + cLN -> left padding (P - 1) d -> two
+ * nn.Conv1d(H, M, P, dilation=d), output_conv1d and skip_conv1d.  With the activation UNFOLDED over the taps into rows c P + p, a weight
+ * (M, H, P) is -- in place -- the row-major (M, H P) matrix of a 1x1 product, so both convolutions, their input gradient ([Wo; Ws]^T product,
+ * then the adjoint fold) and their weight gradients (sep_pw_wgrad, already in the parameters' layout) are the separable layers' products.
+ *   sep_unfold_dilated      cols[b][c P + p][t] = x[b][c][t + p dil - pad] where t < T and 0 <= t + p dil - pad < T, ZERO elsewhere, every
+ *                           column of [T, ldt) included.  x (B, C, ldt), cols (B, C P, ldt), ldt % 4 == 0; any P >= 1, dil >= 1,
+ *                           0 <= pad <= (P - 1) dil (the causal layers: pad = (P - 1) dil).  Columns [T, ldt) of x may hold anything (NaN
+ *                           included) and do not reach the output.  Copies only: the result is exact.
+ *   sep_fold_dilated        the adjoint: dx[b][c][u] = sum_p dcols[b][c P + p][u - p dil + pad] over the p whose column u - p dil + pad lies in
+ *                           [0, T), added in ascending p; ZERO for T <= u < ldt.  A gather: one writer per element, no atomics, bit-stable.
+ *                           Columns [T, ldt) of dcols may hold anything.
+ *   sep_online_unfold_fwd   (+ _sel, _rag) sep_online_depthwise_fwd without its taps: cols[c P + p][column of (stream, f)] = ext[f + p d],
+ *                           ext = [ring (P - 1) d | x]; the ring then takes the last (P - 1) d frames of ext.  cols (C P, ldt).  The ring layout,
+ *                           ring_stride, the slot list, offs and every ownership rule are sep_online_depthwise_fwd's; columns beyond the last
+ *                           block are written as zero in all C P rows.  Any P >= 1, (P - 1) d <= 16384; ring may be NULL when P == 1. */
+int sep_unfold_dilated(const float* x, float* cols, int B, int C, int T, int ldt, int P, int dil, int pad, sep_stream_t stream);
+int sep_fold_dilated(const float* dcols, float* dx, int B, int C, int T, int ldt, int P, int dil, int pad, sep_stream_t stream);
+int sep_online_unfold_fwd(const float* x, float* ring, int64_t ring_stride, float* cols, int num_streams, int C, int n, int ldt, int P, int dilation,
+                          sep_stream_t stream);
+int sep_online_unfold_fwd_sel(const float* x, float* ring, int64_t ring_stride, float* cols, int num_streams, int C, int n, int ldt, int P,
+                              int dilation, const int32_t* slots, sep_stream_t stream);
+int sep_online_unfold_fwd_rag(const float* x, float* ring, int64_t ring_stride, float* cols, int num_streams, int C, int n_cap, int ldt, int P,
+                              int dilation, const int32_t* slots, const int32_t* offs, sep_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
