@@ -12,6 +12,8 @@
 //   sep_online_decoder_fwd    mask * w, synthesis and overlap-add into [tail | n S]: n S final samples, new tail -> tail_next
 //   sep_online_advance        frame counters += n, carry <- carry_next, tail <- tail_next (the last launch of a chunk)
 //   sep_online_reset          zero the state of the streams a device mask selects
+//   sep_online_state_export   the whole state of the streams a slot list names -> one packed row each of a caller's blob (format in sepkernels.h)
+//   sep_online_state_import   the inverse: rows of a blob -> the state of the named streams (any other separator of the same model structure)
 // Every entry point of a chunk has a sibling sep_online_*_sel that takes `const int32_t* slots` (device memory, num_streams distinct entries):
 // the pass then has num_streams column blocks and block j works on the state rows of stream slots[j], so a separator with many slots runs
 // a chunk of the few that have audio.  Both forms are the same kernel templates; without a slot list block j works on stream j.
@@ -359,6 +361,80 @@ __global__ __launch_bounds__(256) void online_reset_kernel(const uint8_t* __rest
     for (int64_t g = g0; g < tail_len; g += step) tail[(size_t)s * tail_len + g] = 0.f;
 }
 
+// ---- export / import of per-stream state (row format, version 1: include/sepkernels.h) ----
+// Byte offsets of the sections of one packed row.  frames and sums are 8-byte words; rings starts on a 16-byte boundary, carry and tail follow
+// it without gaps (4-byte words); the row ends on a 16-byte boundary.
+struct state_layout {
+    int64_t rings, carry, tail, end, row_bytes;
+};
+__host__ __device__ inline state_layout state_layout_of(int carry_len, int sums_len, int64_t rings_len, int tail_len) {
+    state_layout o;
+    o.rings = (8 + 8 * (int64_t)sums_len + 15) / 16 * 16;
+    o.carry = o.rings + 4 * rings_len;
+    o.tail = o.carry + 4 * (int64_t)carry_len;
+    o.end = o.tail + 4 * (int64_t)tail_len;
+    o.row_bytes = (o.end + 15) / 16 * 16;
+    return o;
+}
+
+// len 4-byte words src -> dst as INTEGER words (every bit pattern arrives unchanged), thread g0 of `step`.  The access width follows the real
+// alignment of BOTH sides: 16 bytes where both are 16-byte aligned (rings with H % 16 == 0, every section at paper size), else 8, else 4; the
+// words behind the last whole vector go one by one.  The choice is uniform over a workgroup (it depends on the row only).
+__device__ __forceinline__ void state_copy_words(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, const int64_t len, const int64_t g0,
+                                                 const int64_t step) {
+    const uintptr_t both = (uintptr_t)dst | (uintptr_t)src;
+    int64_t done = 0;
+    if ((both & 15) == 0) {
+        const int64_t nv = len >> 2;
+        for (int64_t g = g0; g < nv; g += step) reinterpret_cast<uint4*>(dst)[g] = reinterpret_cast<const uint4*>(src)[g];
+        done = nv << 2;
+    } else if ((both & 7) == 0) {
+        const int64_t nv = len >> 1;
+        for (int64_t g = g0; g < nv; g += step) reinterpret_cast<uint2*>(dst)[g] = reinterpret_cast<const uint2*>(src)[g];
+        done = nv << 1;
+    }
+    for (int64_t g = done + g0; g < len; g += step) dst[g] = src[g];
+}
+
+// grid (G, num_streams): the G workgroups of row j share the sections of stream slots[j], each thread its stride of every section.
+// IMPORT = false: state -> row j of blob, padding bytes written as zero, nothing beyond row_bytes;  IMPORT = true: row j -> state.
+// Every word has one writer and no word is read and written in the same launch (blob and state do not overlap), so no barrier is needed.
+template <bool IMPORT>
+__global__ __launch_bounds__(256) void online_state_kernel(const int32_t* __restrict__ slots, int64_t* frames, float* carry, int carry_len, double* sums,
+                                                           int sums_len, float* rings, int64_t rings_len, float* tail, int tail_len,
+                                                           unsigned char* blob, int64_t row_pitch) {
+    const int64_t st = slots[blockIdx.y];
+    unsigned char* row = blob + (int64_t)blockIdx.y * row_pitch;
+    const state_layout lay = state_layout_of(carry_len, sums_len, rings_len, tail_len);
+    const int64_t g0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    uint64_t* head = reinterpret_cast<uint64_t*>(row);                   // [frames | sums_len doubles | zero up to the 16-byte boundary]
+    uint64_t* fr = reinterpret_cast<uint64_t*>(frames) + st;
+    uint64_t* sm = reinterpret_cast<uint64_t*>(sums) + st * sums_len;
+    uint32_t* rg = reinterpret_cast<uint32_t*>(rings) + st * rings_len;
+    uint32_t* cr = reinterpret_cast<uint32_t*>(carry) + st * carry_len;
+    uint32_t* tl = reinterpret_cast<uint32_t*>(tail) + st * tail_len;
+    uint32_t* brg = reinterpret_cast<uint32_t*>(row + lay.rings);
+    uint32_t* bcr = reinterpret_cast<uint32_t*>(row + lay.carry);
+    uint32_t* btl = reinterpret_cast<uint32_t*>(row + lay.tail);
+    if constexpr (IMPORT) {
+        if (g0 == 0) fr[0] = head[0];
+        for (int64_t g = g0; g < sums_len; g += step) sm[g] = head[1 + g];
+        state_copy_words(rg, brg, rings_len, g0, step);
+        state_copy_words(cr, bcr, carry_len, g0, step);
+        state_copy_words(tl, btl, tail_len, g0, step);
+    } else {
+        if (g0 == 0) {
+            head[0] = fr[0];
+            for (int64_t b = 8 + 8 * (int64_t)sums_len; b < lay.rings; b += 8) head[b >> 3] = 0;
+            for (int64_t b = lay.end; b < lay.row_bytes; b += 4) *reinterpret_cast<uint32_t*>(row + b) = 0u;
+        }
+        for (int64_t g = g0; g < sums_len; g += step) head[1 + g] = sm[g];
+        state_copy_words(brg, rg, rings_len, g0, step);
+        state_copy_words(bcr, cr, carry_len, g0, step);
+        state_copy_words(btl, tl, tail_len, g0, step);
+    }
+}
+
 inline int ceil_div_i(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 }  // namespace
@@ -576,4 +652,44 @@ extern "C" int sep_online_reset(const uint8_t* mask, int num_streams, int64_t* f
                        sums, sums_len, rings, rings_len, tail, tail_len);
     SEP_CHECK_LAUNCH("sep_online_reset");
     return 0;
+}
+
+extern "C" size_t sep_online_state_row_bytes(int carry_len, int sums_len, int64_t rings_len, int tail_len) {
+    if (carry_len < 0 || sums_len < 0 || rings_len < 0 || tail_len < 0) return 0;
+    return (size_t)state_layout_of(carry_len, sums_len, rings_len, tail_len).row_bytes;
+}
+
+// both directions: the checks, then ONE launch of grid (G, num_streams), G workgroups per row with >= 4 16-byte vectors per thread where the row is long
+static int online_state(const char* who, bool import, const int32_t* slots, int num_streams, int64_t* frames, float* carry, int carry_len, double* sums,
+                        int sums_len, float* rings, int64_t rings_len, float* tail, int tail_len, unsigned char* blob, int64_t row_pitch,
+                        sep_stream_t stream) {
+    SEP_REQUIRE(slots && frames && blob && num_streams > 0 && num_streams <= 65535 && carry_len >= 0 && sums_len >= 0 && rings_len >= 0 && tail_len >= 0,
+                "%s: bad arguments", who);
+    SEP_REQUIRE((carry || carry_len == 0) && (sums || sums_len == 0) && (rings || rings_len == 0) && (tail || tail_len == 0), "%s: state buffer missing",
+                who);
+    const int64_t row_bytes = state_layout_of(carry_len, sums_len, rings_len, tail_len).row_bytes;
+    SEP_REQUIRE(row_pitch >= row_bytes, "%s: row_pitch %lld < the %lld bytes of a row", who, (long long)row_pitch, (long long)row_bytes);
+    SEP_REQUIRE(row_pitch % 16 == 0, "%s: row_pitch %lld is not a multiple of 16", who, (long long)row_pitch);
+    SEP_REQUIRE((uintptr_t)blob % 16 == 0, "%s: blob is not 16-byte aligned", who);
+    const int g = ceil_div_i(row_bytes / 16, 256 * 4);
+    const auto kern = import ? online_state_kernel<true> : online_state_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(g > 256 ? 256 : g, num_streams), dim3(256), 0, (hipStream_t)stream, slots, frames, carry, carry_len, sums, sums_len,
+                       rings, rings_len, tail, tail_len, blob, row_pitch);
+    SEP_CHECK_LAUNCH(who);
+    return 0;
+}
+
+extern "C" int sep_online_state_export(const int32_t* slots, int num_streams, const int64_t* frames, const float* carry, int carry_len,
+                                       const double* sums, int sums_len, const float* rings, int64_t rings_len, const float* tail, int tail_len,
+                                       void* blob, int64_t row_pitch, sep_stream_t stream) {
+    return online_state("sep_online_state_export", false, slots, num_streams, const_cast<int64_t*>(frames), const_cast<float*>(carry), carry_len,
+                        const_cast<double*>(sums), sums_len, const_cast<float*>(rings), rings_len, const_cast<float*>(tail), tail_len,
+                        static_cast<unsigned char*>(blob), row_pitch, stream);
+}
+
+extern "C" int sep_online_state_import(const int32_t* slots, int num_streams, int64_t* frames, float* carry, int carry_len, double* sums, int sums_len,
+                                       float* rings, int64_t rings_len, float* tail, int tail_len, const void* blob, int64_t row_pitch,
+                                       sep_stream_t stream) {
+    return online_state("sep_online_state_import", true, slots, num_streams, frames, carry, carry_len, sums, sums_len, rings, rings_len, tail, tail_len,
+                        static_cast<unsigned char*>(const_cast<void*>(blob)), row_pitch, stream);
 }

@@ -227,9 +227,14 @@ SIGNATURES = {
     "sep_online_unfold_fwd": [_vp, _vp, _L, _vp] + [_I] * 6 + [_vp],
     "sep_online_unfold_fwd_sel": [_vp, _vp, _L, _vp] + [_I] * 6 + [_vp, _vp],
     "sep_online_unfold_fwd_rag": [_vp, _vp, _L, _vp] + [_I] * 6 + [_vp, _vp, _vp],
+    # export / import of the online separator's per-stream state (ABI 23, additive): slots, num_streams, the five state buffers with their
+    # per-stream lengths as sep_online_reset takes them, blob, row_pitch
+    "sep_online_state_row_bytes": [_I, _I, _L, _I],                  # returns size_t
+    "sep_online_state_export": [_vp, _I, _vp, _vp, _I, _vp, _I, _vp, _L, _vp, _I, _vp, _L, _vp],
+    "sep_online_state_import": [_vp, _I, _vp, _vp, _I, _vp, _I, _vp, _L, _vp, _I, _vp, _L, _vp],
 }
 _RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_last_kernel": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
-             "sep_gln_tokens_ws_bytes": ctypes.c_size_t}
+             "sep_gln_tokens_ws_bytes": ctypes.c_size_t, "sep_online_state_row_bytes": ctypes.c_size_t}
 
 _lib = None
 
@@ -868,6 +873,21 @@ class HipBackend:
         _check(load().sep_online_advance_rag(_ptr(frames, torch.int64), _ptr(carry, _f32), _ptr(carry_next, _f32), carry_len, _ptr(tail, _f32),
                                              _ptr(tail_next, _f32), tail_len, num_streams, n_cap, _ptr(slots, torch.int32), _ptr(offs, torch.int32),
                                              _stream()), "sep_online_advance_rag")
+
+    # ... export / import of per-stream state: `slots` (int32 on the device) names the streams, row j of `blob` (uint8, rows `row_pitch` bytes
+    # apart) is the packed state of stream slots[j] (the row format: include/sepkernels.h)
+    def online_state_row_bytes(self, carry_len, sums_len, rings_len, tail_len):
+        return int(load().sep_online_state_row_bytes(carry_len, sums_len, rings_len, tail_len))
+
+    def online_state_export(self, slots, num_streams, frames, carry, carry_len, sums, sums_len, rings, rings_len, tail, tail_len, blob, row_pitch):
+        _check(load().sep_online_state_export(_ptr(slots, torch.int32), num_streams, _ptr(frames, torch.int64), _ptr(carry, _f32), carry_len,
+                                              _ptr(sums, _f64), sums_len, _ptr(rings, _f32), rings_len, _ptr(tail, _f32), tail_len,
+                                              _ptr(blob, torch.uint8), row_pitch, _stream()), "sep_online_state_export")
+
+    def online_state_import(self, slots, num_streams, frames, carry, carry_len, sums, sums_len, rings, rings_len, tail, tail_len, blob, row_pitch):
+        _check(load().sep_online_state_import(_ptr(slots, torch.int32), num_streams, _ptr(frames, torch.int64), _ptr(carry, _f32), carry_len,
+                                              _ptr(sums, _f64), sums_len, _ptr(rings, _f32), rings_len, _ptr(tail, _f32), tail_len,
+                                              _ptr(blob, torch.uint8), row_pitch, _stream()), "sep_online_state_import")
 
 
 _backend = HipBackend()

@@ -60,6 +60,20 @@ sep_online_*_rag entry points read it when they run).  The step is the launch li
 the dead columns [offs[A], ldt) are zero wherever a state kernel wrote, only ever feed themselves, and no state kernel nor the decoder reads
 them -- so the launch arguments depend on (A, ldt, W) only: a ragged call with W == chunk_size is recorded per (A, ldt) and replayed for ANY
 lengths with that total, under the same `max_recordings` bound.  Other widths run eagerly.
+
+State that travels.  Everything a slot carries from call to call can leave the separator it started in and come back, for some slots while the
+others keep running:
+
+    state = sep.export_state([3, 1])     # OnlineState: row 0 is slot 3, row 1 slot 1; the separator is not changed
+    other.import_state(state[0], [1])    # slot 1 of ANOTHER separator of the same model structure goes on where slot 3 was (migration)
+    torch.save(state.cpu().state_dict(), f);  state = OnlineState.from_state_dict(torch.load(f))       # tensors and builtin values only
+    sep.import_state(state, [3, 1])      # back to the moment of the export: the same calls then give the same bits again (rollback)
+
+A state is one (A, row_bytes) uint8 tensor -- one packed row per slot, written and read by ONE launch each (sep_online_state_export /
+sep_online_state_import, the row format is documented in include/sepkernels.h as version 1) -- plus a header of plain Python values that
+import_state compares with its own separator before anything is uploaded.  Import writes into the existing state buffers in place, so every
+recorded step stays valid.  An imported slot behaves exactly as the exported one would have; flush, reset, subset and ragged calls are
+unchanged.  Whether the WEIGHTS are the same cannot be checked cheaply and is not checked.
 """
 import collections
 
@@ -128,6 +142,81 @@ class _SubsetWorkspace:
         return v
 
 
+STATE_FORMAT_VERSION = 1                                   # the row format of include/sepkernels.h ("export / import of the online separator's per-stream state")
+_HEADER_KEYS = ("version", "L", "S", "n_sources", "n_norms", "ring_len", "separable", "config", "dtype")
+
+
+class OnlineState:
+    """The state of A slots of an OnlineSeparator, taken by export_state: `blob`, an (A, row_bytes) uint8 tensor with one packed row per slot
+    (row format `version`, include/sepkernels.h), and a header of plain Python values that says which separators can take it -- `version`,
+    `L`, `S`, `n_sources`, `n_norms`, `ring_len`, `separable`, `config` (the model's get_config()) and `dtype` (a string).  It owns its
+    blob: nothing in it refers to the separator it came from.
+
+    len(state)              the number of rows
+    state.frames            (A,) int64, the frame counter of every row, decoded from the blob on request (on the blob's device)
+    state.to(device), state.cpu()
+    state[i], state.select(rows)    a state of the chosen rows (an index, a slice, or a list / tensor of indices), in that order
+    state.state_dict(), OnlineState.from_state_dict(d)      a dict of one tensor and builtin values: it survives torch.save / torch.load"""
+
+    def __init__(self, blob, header):
+        missing = [k for k in _HEADER_KEYS if k not in header]
+        if missing:
+            raise ValueError("an online state's header lacks {}".format(missing))
+        if not torch.is_tensor(blob):
+            raise ValueError("an online state's blob is a tensor (got {})".format(type(blob).__name__))
+        self.blob = blob
+        self.header = {k: header[k] for k in _HEADER_KEYS}
+
+    def __getattr__(self, name):                               # state.version, state.L, ... : the header's entries
+        header = self.__dict__.get("header")
+        if header is not None and name in header:
+            return header[name]
+        raise AttributeError(name)
+
+    def __len__(self):
+        return self.blob.shape[0]
+
+    @property
+    def frames(self):
+        if self.blob.dim() != 2 or self.blob.dtype != torch.uint8 or self.blob.shape[1] < 8:
+            raise ValueError("the blob is not a (rows, row_bytes) uint8 tensor: it holds no frame counters")
+        return self.blob[:, :8].contiguous().view(torch.int64).reshape(-1)
+
+    def to(self, device):
+        return OnlineState(self.blob.to(device), self.header)
+
+    def cpu(self):
+        return self.to("cpu")
+
+    def select(self, rows):
+        if torch.is_tensor(rows):
+            rows = rows.reshape(-1).tolist()
+        rows = [int(r) for r in rows]
+        if any(r < -len(self) or r >= len(self) for r in rows):
+            raise IndexError("row out of range: the state has {} rows".format(len(self)))
+        return OnlineState(self.blob[[r % len(self) for r in rows]] if rows else self.blob[:0].clone(), self.header)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return self.select(list(range(len(self)))[i])
+        if isinstance(i, int):
+            return self.select([i])
+        return self.select(i)
+
+    def state_dict(self):
+        d = {"format_version" if k == "version" else k: (dict(v) if k == "config" else v) for k, v in self.header.items()}
+        d["blob"] = self.blob
+        return d
+
+    @classmethod
+    def from_state_dict(cls, d):
+        header = dict(d)
+        blob = header.pop("blob", None)
+        if "format_version" in header:
+            header["version"] = header.pop("format_version")
+        return cls(blob, header)
+
+
 class OnlineSeparator:
     """Chunk-by-chunk separation of `num_streams` independent mono streams by a causal Conv-TasNet (see the module docstring for the contract).
     Built by ConvTasNet.online_separator; reads the model's live parameters at every chunk (an in-place update or load_state_dict is seen at
@@ -194,6 +283,7 @@ class OnlineSeparator:
         self._sub_seqs = collections.OrderedDict()             # A (subset step) or (A, ldt) (ragged step) -> Sequence at chunk_size, least recently used first
         self.replays = collections.Counter()                   # recording key -> how often it was replayed
         self._sub_flat = None
+        self._state_slots = None                               # export_state / import_state: the slot list on the device, filled before every call
 
     # ------------------------------------------------------------------ public
     def __call__(self, chunk, streams=None, lengths=None):
@@ -266,6 +356,65 @@ class OnlineSeparator:
         with torch.no_grad():
             backend().online_reset(mask, Bs, self.frames, self.carry if keep else None, keep, self.sums, 2 * self.n_norms,
                                    self.rings if self.ring_len else None, self.ring_len, self.tail if keep else None, self.n_src * keep)
+
+    # ------------------------------------------------------------------ state that travels
+    def _state_header(self):
+        return dict(version=STATE_FORMAT_VERSION, L=self.L, S=self.S, n_sources=self.n_src, n_norms=self.n_norms, ring_len=self.ring_len,
+                    separable=not self.dense, config=self.model.get_config(), dtype=str(self.dtype).replace("torch.", ""))
+
+    def _state_args(self, idx):
+        """-> the arguments both state entry points share, the slot list uploaded"""
+        keep, A = self.delay, len(idx)
+        if self._state_slots is None:
+            self._state_slots = torch.zeros(self.num_streams, device=self.device, dtype=torch.int32)
+        self._state_slots[:A].copy_(torch.tensor(idx, dtype=torch.int32))
+        return (self._state_slots, A, self.frames, self.carry if keep else None, keep, self.sums, 2 * self.n_norms,
+                self.rings if self.ring_len else None, self.ring_len, self.tail if keep else None, self.n_src * keep)
+
+    def _state_row_bytes(self):
+        return backend().online_state_row_bytes(self.delay, 2 * self.n_norms, self.ring_len, self.n_src * self.delay)
+
+    def export_state(self, streams=None):
+        """-> OnlineState: row j holds everything slot streams[j] carries from call to call (frame counter, cLN sums, histories, encoder carry,
+        overlap-add tail).  `streams` is what sep(chunk, streams=...) accepts (None: all slots in order).  One launch; the separator is not
+        changed, and the state does not refer to it afterwards."""
+        idx = list(range(self.num_streams)) if streams is None else self._select(streams)
+        row_bytes = self._state_row_bytes()
+        with torch.no_grad():
+            blob = torch.empty(len(idx), row_bytes, device=self.device, dtype=torch.uint8)      # the kernel writes every byte of a row, padding included
+            backend().online_state_export(*self._state_args(idx), blob, row_bytes)
+        return OnlineState(blob, self._state_header())
+
+    def import_state(self, state, streams=None):
+        """Slot streams[j] takes row j of `state` (None: slots 0 .. len(state) - 1, and len(state) must then be num_streams) and goes on exactly as
+        the exported slot would have: the same calls give the same bits.  The separator may have any num_streams and need not be the one that
+        exported; a state on another device is moved first.  One launch, into the existing state buffers in place: recorded steps stay valid, no
+        slot that is not named is written.  A header that does not match this separator's model structure, dtype or format version, a row count
+        that does not match the selection, a duplicate or out-of-range slot and a blob of the wrong shape or dtype are ValueErrors raised
+        before anything is uploaded or launched.  Whether the model's WEIGHTS are those of the exporting one cannot be checked cheaply and is
+        NOT checked: a state imported under other weights continues as a stream that never existed."""
+        if not isinstance(state, OnlineState):
+            raise ValueError("import_state takes an OnlineState (got {})".format(type(state).__name__))
+        own = self._state_header()
+        for k in _HEADER_KEYS:
+            if state.header[k] != own[k]:
+                if k == "version":
+                    raise ValueError("the state has format version {}, this separator reads version {}".format(state.header[k], own[k]))
+                raise ValueError("the state does not fit this separator: its {} is {!r}, the separator's {!r}".format(k, state.header[k], own[k]))
+        blob, row_bytes = state.blob, self._state_row_bytes()
+        if blob.dtype != torch.uint8 or blob.dim() != 2 or blob.shape[1] != row_bytes:
+            raise ValueError("the state's blob must be a (rows, {}) uint8 tensor (got {} {})".format(row_bytes, tuple(blob.shape), blob.dtype))
+        if streams is None:
+            if len(state) != self.num_streams:
+                raise ValueError("the state has {} rows, the separator {} slots: name the slots that take them".format(len(state), self.num_streams))
+            idx = list(range(self.num_streams))
+        else:
+            idx = self._select(streams)
+            if len(idx) != len(state):
+                raise ValueError("{} rows of state for {} selected streams: every stream takes one".format(len(state), len(idx)))
+        with torch.no_grad():
+            blob = blob.to(self.device).contiguous()
+            backend().online_state_import(*self._state_args(idx), blob, row_bytes)
 
     # ------------------------------------------------------------------ a call on a selection of the streams
     def _select(self, streams):

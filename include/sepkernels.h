@@ -692,6 +692,47 @@ int sep_online_unfold_fwd_sel(const float* x, float* ring, int64_t ring_stride, 
 int sep_online_unfold_fwd_rag(const float* x, float* ring, int64_t ring_stride, float* cols, int num_streams, int C, int n_cap, int ldt, int P,
                               int dilation, const int32_t* slots, const int32_t* offs, sep_stream_t stream);
 
+/* ---- export / import of the online separator's per-stream state (ABI 23, additive; csrc/online.hip) ------------------------------------------
+ * The five state buffers above (frames, carry, sums, rings, tail; carry_len, sums_len, rings_len, tail_len are the element counts PER STREAM, the
+ * vocabulary of sep_online_reset) hold everything a stream carries from chunk to chunk.  These entry points move the complete state of the
+ * streams a slot list names into a caller's blob and back, so a stream can leave the buffers it started in: migrate to other buffers (another
+ * number of slots, another process, another GPU via the host), persist, or be rewound to an earlier export -- for some slots while the others
+ * keep running.  carry_next / tail_next are not part of the state: sep_online_advance is the last launch of every chunk, between two chunks
+ * they are scratch, and neither entry point takes or touches them.
+ * ROW FORMAT, VERSION 1.  One stream is one row of sep_online_state_row_bytes(carry_len, sums_len, rings_len, tail_len) bytes, little endian,
+ * the sections in this order and at these byte offsets:
+ *        0                      int64   frames
+ *        8                      double  sums[sums_len]
+ *        8 + 8 sums_len         zero bytes up to the next multiple of 16 =: R
+ *        R                      float   rings[rings_len]
+ *        R + 4 rings_len        float   carry[carry_len]
+ *        .. + 4 carry_len       float   tail[tail_len]
+ *        .. + 4 tail_len        zero bytes up to the next multiple of 16 = row_bytes
+ * so rings, the large section, starts on a 16-byte boundary of a 16-byte aligned row (H % 16 == 0 makes rings_len a multiple of 16 floats, and
+ * carry and tail then start on one too when their lengths are multiples of 4).  A format that lays a row out differently gets another version
+ * number; the number is kept by the caller next to the blob (sepkernels/online.py: OnlineState.version), not inside the rows.
+ *   sep_online_state_row_bytes   the size of one row, a multiple of 16 (0 for a negative length).  Not a launch: no stream, no sequence-table entry.
+ *   sep_online_state_export      row j of blob, at byte j * row_pitch, receives the state of stream slots[j]; the padding bytes inside a row are
+ *                                written as zero; bytes [row_bytes, row_pitch) of a row are left untouched.  Nothing of a stream that slots does not
+ *                                name is read.  The state buffers are not changed.
+ *   sep_online_state_import      the exact inverse: the state of stream slots[j] receives row j.  No entry of a stream that slots does not name is
+ *                                written.  The buffers may belong to another separator than the exporting one (another number of streams, other
+ *                                slots) as long as the four lengths are the same; whether the MODEL is the same the library cannot know.
+ * slots is device memory of num_streams (<= 65535) distinct entries inside the state buffers, read when the kernel runs (a recorded call replays
+ * for whatever the buffer holds by then); duplicates or entries out of range are undefined, as for the _sel entry points.  blob is device memory,
+ * 16-byte aligned, row_pitch >= row_bytes and row_pitch % 16 == 0; it must not overlap the state buffers.  A length may be zero (L == S: no carry,
+ * no tail; a model without history: no rings) and its pointer then NULL.  Each call is ONE launch, grid (G, num_streams) with G workgroups
+ * sharing a row; the sections are copied as integer words -- never through floating-point arithmetic, so every bit pattern (NaN payloads,
+ * denormals) arrives unchanged -- in the widest of 16-, 8- and 4-byte accesses that the alignment of both sides of a section allows (carry_len
+ * need not be a multiple of 4).  No atomics; all offsets are 64-bit (1024 streams x 3.13 MB exceeds 2^32 bytes).  Ownership: a caller that binds
+ * the C ABI directly owns blob and the state buffers; the library keeps no copy and no pointer. */
+size_t sep_online_state_row_bytes(int carry_len, int sums_len, int64_t rings_len, int tail_len);
+int sep_online_state_export(const int32_t* slots, int num_streams, const int64_t* frames, const float* carry, int carry_len, const double* sums,
+                            int sums_len, const float* rings, int64_t rings_len, const float* tail, int tail_len, void* blob, int64_t row_pitch,
+                            sep_stream_t stream);
+int sep_online_state_import(const int32_t* slots, int num_streams, int64_t* frames, float* carry, int carry_len, double* sums, int sums_len,
+                            float* rings, int64_t rings_len, float* tail, int tail_len, const void* blob, int64_t row_pitch, sep_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,8 +24,14 @@ the grouped route costs.  To time the grouped route on a commit that has no --ra
 commit into a directory of its own, build it there, copy THIS file over its tools/bench_online.py (the tool finds the package relative to itself)
 and run it there with --ragged --routes grouped.
 
+With --state nothing of the above runs either.  For the same (A, slots) pairs it times sep.export_state(idx) and sep.import_state(state, idx) of
+A of the slots at paper size, a fresh selection of A slots at every call (drawn before the clock starts), HIP events around the whole call
+(the upload of the slot list, the allocation of the blob and the one launch), synchronised per call.  One JSON line per pair: row_bytes,
+export_ms_median / _p99, import_ms_median / _p99, bytes_moved_per_call (A row_bytes read plus A row_bytes written) and the GB/s that makes.
+
     python tools/bench_online.py [--streams 1,16,64,256,1024] [--chunks 80,160,800] [--active 64,256] [--reps 200] [--eager-reps 200] [--out FILE]
     python tools/bench_online.py --ragged [--routes ragged,grouped] [--reps 200] [--out FILE]
+    python tools/bench_online.py --state [--reps 200] [--out FILE]
 """
 import argparse
 import json
@@ -126,6 +132,32 @@ def _ragged(torch, sepkernels, model, args):
     return lines
 
 
+def _state(torch, sepkernels, model, args):
+    warm, lines = 10, []
+    for A, Bs in RAGGED:
+        sep = model.online_separator(num_streams=Bs, chunk_size=RAGGED_CHUNK)
+        g = torch.Generator().manual_seed(1)
+        picks = [torch.randperm(Bs, generator=g)[:A].tolist() for _ in range(warm + args.reps)]
+        for t in (sep.carry, sep.rings, sep.tail):                     # a state that is not all zeros (the copies do not care)
+            t.normal_()
+        sep.sums.normal_()
+        sep.frames.fill_(12345)
+        held = []
+        emed, ep99 = _tick_times(torch, lambda k: held.__setitem__(slice(None), [sep.export_state(picks[k])]), args.reps, warm)
+        state = held[0]
+        imed, ip99 = _tick_times(torch, lambda k: sep.import_state(state, picks[k]), args.reps, warm)
+        moved = 2 * A * state.blob.shape[1]
+        row = dict(model="convtasnet_causal_paper", slots=Bs, active=A, row_bytes=state.blob.shape[1], bytes_moved_per_call=moved,
+                   export_ms_median=round(emed, 4), export_ms_p99=round(ep99, 4), import_ms_median=round(imed, 4), import_ms_p99=round(ip99, 4),
+                   export_gb_per_s=round(moved / (emed * 1e6), 1), import_gb_per_s=round(moved / (imed * 1e6), 1), reps=args.reps,
+                   device=torch.cuda.get_device_name(0))
+        print(json.dumps(row), flush=True)
+        lines.append(row)
+        del sep, state, held
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", default="1,16,64,256,1024")
@@ -136,6 +168,7 @@ def main():
     ap.add_argument("--out", default=None, help="also write the lines to this file")
     ap.add_argument("--ragged", action="store_true", help="time ragged calls (a length per stream) and the grouped route instead")
     ap.add_argument("--routes", default="ragged,grouped", help="with --ragged: which routes to time")
+    ap.add_argument("--state", action="store_true", help="time export_state / import_state of A of the slots instead")
     args = ap.parse_args()
     import torch
     import sepkernels
@@ -146,7 +179,10 @@ def main():
     model = ConvTasNet(**PAPER).cuda()
     assert model.staged and not model.fused
     lines = []
-    if args.ragged:
+    if args.state:
+        lines = _state(torch, sepkernels, model, args)
+        args.streams = ""
+    elif args.ragged:
         lines = _ragged(torch, sepkernels, model, args)
         args.streams = ""
     for B in [int(v) for v in args.streams.split(",") if v]:
