@@ -453,6 +453,199 @@ extern "C" int sep_adam_step(float* p, float* g, float* m, float* v, const doubl
     return 0;
 }
 
+// ---- BSS-eval v3 ("sources"): the O(T) parts of SDR / SIR / SAR -------------------------------------------------------------------------
+// Reference arithmetic replaced: src/utils/bss.py:4-30 (a wrapper of mir_eval.separation.bss_eval_sources), called per utterance by
+// egs/wsj0-mix/common/src/driver.py:291-309.  The metric projects every estimate on the span of the references delayed by 0 .. flen - 1
+// samples (normal equations) and compares energies.  Two O(T flen) passes are kernels here -- the lagged correlations that fill the normal
+// equations and the FIR pass that turns the solved filters into the five energies of a pair; the (n flen)^2 solve between them is the
+// caller's (utils/bss.py).  fp64 arithmetic on fp32 audio.  No atomics: every workgroup owns one time slab of FIXED size and writes its partial
+// sums to the caller's scratch, a second launch adds the slabs in ascending order -- two runs give the same bits, and a row gives the same
+// bits whatever the pitch T and the batch around it are (samples beyond a row's length enter as exact zeros, slabs beyond it as 0.0).
+namespace {
+
+constexpr int BSS_TILE = 256;           // samples staged per step = lags (outputs) per workgroup: one per thread
+constexpr int BSS_XC_SLAB = 2048;       // time samples behind one partial of sep_bss_xcorr
+constexpr int BSS_EN_SLAB = 1024;       // output samples behind one partial of sep_bss_energies
+constexpr int BSS_MAX_T = 1 << 30;
+
+__device__ __forceinline__ int bss_row_length(const int32_t* lengths, const int b, const int T) {
+    if (!lengths) return T;
+    const int v = lengths[b];
+    return v < 0 ? 0 : (v > T ? T : v);
+}
+
+static inline int64_t bss_slabs(const int64_t len, const int slab) { return (len + slab - 1) / slab; }
+
+// part[b][i][k][slab][l] = sum over the slab's t of a[b][i][t] c[b][k][t + lag_lo + l].  grid (nslab * lag tiles, n m, B).
+// a_s holds the tile of a, c_s the 2 BSS_TILE - 1 samples of c that BSS_TILE lags of it touch: a_s[tt] is one address for the whole wave (a
+// broadcast), c_s[tt + lane] consecutive doubles (no bank conflict).
+__global__ __launch_bounds__(256) void bss_xcorr_kernel(const float* __restrict__ a, const float* __restrict__ c, double* __restrict__ part,
+                                                        const int32_t* __restrict__ lengths, const int n, const int m, const int T,
+                                                        const int lag_lo, const int nlag, const int nslab) {
+    __shared__ double a_s[BSS_TILE];
+    __shared__ double c_s[2 * BSS_TILE];
+    const int tid = threadIdx.x, b = blockIdx.z, i = blockIdx.y / m, k = blockIdx.y % m;
+    const int slab = blockIdx.x % nslab, l0 = (blockIdx.x / nslab) * BSS_TILE;
+    const int Tb = bss_row_length(lengths, b, T);
+    const float* ar = a + ((int64_t)b * n + i) * T;
+    const float* cr = c + ((int64_t)b * m + k) * T;
+    const int64_t shift = (int64_t)lag_lo + l0;                         // c_s[q] = c[t0 + shift + q]
+    const int64_t t_end = (int64_t)(slab + 1) * BSS_XC_SLAB < Tb ? (int64_t)(slab + 1) * BSS_XC_SLAB : Tb;
+    double acc = 0.0;
+    for (int64_t t0 = (int64_t)slab * BSS_XC_SLAB; t0 < t_end; t0 += BSS_TILE) {
+        a_s[tid] = t0 + tid < Tb ? (double)ar[t0 + tid] : 0.0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int q = tid + h * BSS_TILE;
+            const int64_t u = t0 + shift + q;
+            c_s[q] = (u >= 0 && u < Tb) ? (double)cr[u] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int tt = 0; tt < BSS_TILE; ++tt) acc = fma(a_s[tt], c_s[tt + tid], acc);
+        __syncthreads();
+    }
+    if (l0 + tid < nlag) part[((((int64_t)b * n + i) * m + k) * nslab + slab) * nlag + l0 + tid] = acc;
+}
+
+// out[o][r] = part[o][0][r] + part[o][1][r] + ... in this order; total = outer * inner
+__global__ __launch_bounds__(256) void bss_reduce_kernel(const double* __restrict__ part, double* __restrict__ out, const int nslab,
+                                                         const int inner, const int64_t total) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int64_t o = e / inner, r = e % inner;
+    double s = 0.0;
+    for (int sl = 0; sl < nslab; ++sl) s += part[(o * nslab + sl) * inner + r];
+    out[e] = s;
+}
+
+// The pair (estimate j, reference i) of sample b, output samples [slab BSS_EN_SLAB, (slab + 1) BSS_EN_SLAB) of the T_b + flen - 1: thread `tid`
+// of a step owns t = t0 + tid and forms P_all(e_j)[t] = sum_k sum_tau fa[j][k][tau] r_k[t - tau] (passes 0 .. n - 1) and
+// P_i(e_j)[t] = sum_tau fo[j][i][tau] r_i[t - tau] (pass n) from staged tiles: r_s[q] = r[t0 - tau0 - (BSS_TILE - 1) + q], so the tap tau0 + x
+// of thread tid reads r_s[tid + BSS_TILE - 1 - x] -- consecutive doubles across the wave, the tap itself a broadcast.  The projected signals
+// live in registers only.  grid (nslab, m n, B).
+__global__ __launch_bounds__(256) void bss_energies_kernel(const float* __restrict__ ref, const float* __restrict__ est,
+                                                           const double* __restrict__ filt_all, const double* __restrict__ filt_one,
+                                                           double* __restrict__ part, const int32_t* __restrict__ lengths, const int n,
+                                                           const int m, const int T, const int flen, const int nslab) {
+    __shared__ double r_s[2 * BSS_TILE];
+    __shared__ double f_s[BSS_TILE];
+    __shared__ double red[4];
+    const int tid = threadIdx.x, b = blockIdx.z, j = blockIdx.y / n, i = blockIdx.y % n, slab = blockIdx.x;
+    const int Tb = bss_row_length(lengths, b, T);
+    const int64_t Tx = Tb > 0 ? (int64_t)Tb + flen - 1 : 0;
+    const int64_t t_end = (int64_t)(slab + 1) * BSS_EN_SLAB < Tx ? (int64_t)(slab + 1) * BSS_EN_SLAB : Tx;
+    const float* er = est + ((int64_t)b * m + j) * T;
+    double e_s = 0.0, e_i = 0.0, e_a = 0.0, e_ia = 0.0, e_si = 0.0;
+    for (int64_t t0 = (int64_t)slab * BSS_EN_SLAB; t0 < t_end; t0 += BSS_TILE) {
+        double pall = 0.0, sf = 0.0;
+        for (int pass = 0; pass <= n; ++pass) {
+            const int k = pass < n ? pass : i;
+            const float* rr = ref + ((int64_t)b * n + k) * T;
+            const double* f = (pass < n ? filt_all : filt_one) + (((int64_t)b * m + j) * n + k) * flen;
+            double acc = 0.0;
+            for (int tau0 = 0; tau0 < flen; tau0 += BSS_TILE) {
+                const int nx = flen - tau0 < BSS_TILE ? flen - tau0 : BSS_TILE;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int q = tid + h * BSS_TILE;
+                    const int64_t u = t0 - tau0 - (BSS_TILE - 1) + q;
+                    r_s[q] = (u >= 0 && u < Tb) ? (double)rr[u] : 0.0;
+                }
+                f_s[tid] = tid < nx ? f[tau0 + tid] : 0.0;
+                __syncthreads();
+#pragma unroll 4
+                for (int x = 0; x < nx; ++x) acc = fma(f_s[x], r_s[tid + BSS_TILE - 1 - x], acc);
+                __syncthreads();
+            }
+            if (pass < n) pall += acc; else sf = acc;
+        }
+        const int64_t t = t0 + tid;
+        if (t < Tx) {
+            const double e = t < Tb ? (double)er[t] : 0.0;
+            const double interf = pall - sf, artif = e - pall;
+            e_s = fma(sf, sf, e_s);
+            e_i = fma(interf, interf, e_i);
+            e_a = fma(artif, artif, e_a);
+            e_ia = fma(interf + artif, interf + artif, e_ia);
+            e_si = fma(sf + interf, sf + interf, e_si);
+        }
+    }
+    const double v[5] = {e_s, e_i, e_a, e_ia, e_si};
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        const double r = block_sum_256<double>(v[q], red);
+        if (tid == 0) part[((((int64_t)b * m + j) * n + i) * nslab + slab) * 5 + q] = r;
+    }
+}
+
+// doubles of scratch one call needs, or -1 where a grid limit is exceeded
+static int64_t bss_xcorr_scratch(const int B, const int n, const int m, const int T, const int nlag) {
+    const int64_t nslab = bss_slabs(T, BSS_XC_SLAB), ntile = bss_slabs(nlag, BSS_TILE);
+    int64_t need = (int64_t)B * n * m;                                  // (< 2^32 once the grid limits hold)
+    if ((int64_t)n * m > 65535 || B > 65535 || nslab * ntile > 0x7fffffff) return -1;
+    if (((int64_t)B * n * m * nlag + 255) / 256 > 0x7fffffff) return -1;   // the grid of the reduction
+    if (__builtin_mul_overflow(need, nslab * nlag, &need) || need > (int64_t)1 << 56) return -1;
+    return need;
+}
+static int64_t bss_energies_scratch(const int B, const int n, const int m, const int T, const int flen) {
+    const int64_t nslab = bss_slabs((int64_t)T + flen - 1, BSS_EN_SLAB);
+    if ((int64_t)n * m > 65535 || B > 65535) return -1;
+    return (int64_t)B * n * m * nslab * 5;
+}
+static bool bss_shape_ok(const int B, const int n, const int m, const int T) { return B >= 1 && n >= 1 && m >= 1 && T >= 1 && T <= BSS_MAX_T; }
+
+}  // namespace
+
+extern "C" size_t sep_bss_scratch_bytes(int B, int n, int m, int T, int flen) {
+    if (!bss_shape_ok(B, n, m, T) || flen < 1 || flen > BSS_MAX_T / 2) return 0;
+    const int64_t need[3] = {bss_xcorr_scratch(B, n, n, T, 2 * flen - 1), bss_xcorr_scratch(B, n, m, T, flen), bss_energies_scratch(B, n, m, T, flen)};
+    int64_t most = 0;
+    for (int q = 0; q < 3; ++q) {
+        if (need[q] < 0) return 0;
+        most = need[q] > most ? need[q] : most;
+    }
+    return (size_t)most * sizeof(double);
+}
+
+extern "C" int sep_bss_xcorr(const float* a, const float* c, const int32_t* lengths, double* out, double* scratch, size_t scratch_bytes, int B,
+                             int n, int m, int T, int lag_lo, int nlag, sep_stream_t stream) {
+    SEP_REQUIRE(a && c && out && scratch, "sep_bss_xcorr: null pointer");
+    SEP_REQUIRE(bss_shape_ok(B, n, m, T) && nlag >= 1 && nlag <= BSS_MAX_T && lag_lo >= -BSS_MAX_T && lag_lo <= BSS_MAX_T,
+                "sep_bss_xcorr: bad arguments (B=%d n=%d m=%d T=%d lag_lo=%d nlag=%d; all counts >= 1, T and the lags within 2^30)", B, n, m, T, lag_lo, nlag);
+    const int64_t need = bss_xcorr_scratch(B, n, m, T, nlag);
+    SEP_REQUIRE(need >= 0, "sep_bss_xcorr: grid limit (B <= 65535, n m <= 65535, slabs x lag tiles < 2^31, B n m nlag < 2^39, scratch < 2^59 bytes)");
+    SEP_REQUIRE(scratch_bytes / sizeof(double) >= (size_t)need, "sep_bss_xcorr: scratch holds %zu bytes, %lld needed", scratch_bytes,
+                (long long)need * (long long)sizeof(double));
+    const int nslab = (int)bss_slabs(T, BSS_XC_SLAB), ntile = (int)bss_slabs(nlag, BSS_TILE);
+    hipLaunchKernelGGL(bss_xcorr_kernel, dim3((unsigned)(nslab * ntile), (unsigned)(n * m), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, c, scratch,
+                       lengths, n, m, T, lag_lo, nlag, nslab);
+    SEP_CHECK_LAUNCH("sep_bss_xcorr");
+    const int64_t total = (int64_t)B * n * m * nlag;
+    hipLaunchKernelGGL(bss_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, out, nslab, nlag, total);
+    SEP_CHECK_LAUNCH("sep_bss_xcorr (reduction)");
+    return 0;
+}
+
+extern "C" int sep_bss_energies(const float* ref, const float* est, const double* filt_all, const double* filt_one, const int32_t* lengths,
+                                double* out, double* scratch, size_t scratch_bytes, int B, int n, int m, int T, int flen, sep_stream_t stream) {
+    SEP_REQUIRE(ref && est && filt_all && filt_one && out && scratch, "sep_bss_energies: null pointer");
+    SEP_REQUIRE(bss_shape_ok(B, n, m, T) && flen >= 1 && flen <= BSS_MAX_T,
+                "sep_bss_energies: bad arguments (B=%d n=%d m=%d T=%d flen=%d; all >= 1, T and flen within 2^30)", B, n, m, T, flen);
+    const int64_t need = bss_energies_scratch(B, n, m, T, flen);
+    SEP_REQUIRE(need >= 0, "sep_bss_energies: grid limit (B <= 65535, n m <= 65535)");
+    SEP_REQUIRE(scratch_bytes / sizeof(double) >= (size_t)need, "sep_bss_energies: scratch holds %zu bytes, %lld needed", scratch_bytes,
+                (long long)need * (long long)sizeof(double));
+    const int nslab = (int)bss_slabs((int64_t)T + flen - 1, BSS_EN_SLAB);
+    hipLaunchKernelGGL(bss_energies_kernel, dim3((unsigned)nslab, (unsigned)(m * n), (unsigned)B), dim3(256), 0, (hipStream_t)stream, ref, est, filt_all,
+                       filt_one, scratch, lengths, n, m, T, flen, nslab);
+    SEP_CHECK_LAUNCH("sep_bss_energies");
+    const int64_t total = (int64_t)B * m * n * 5;
+    hipLaunchKernelGGL(bss_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, out, nslab, 5, total);
+    SEP_CHECK_LAUNCH("sep_bss_energies (reduction)");
+    return 0;
+}
+
 // ---- error plumbing ---------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
 void sep_set_error(const char* fmt, ...) {

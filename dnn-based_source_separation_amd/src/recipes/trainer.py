@@ -187,8 +187,11 @@ class Trainer:
 class Tester:
     __test__ = False        # (not a pytest class)
     """Variable-length inference over a test list: PIT loss, loss improvement over the unprocessed mixture, SI-SDR
-    improvement; writes up to 10 example utterances.  (The reference additionally calls mir_eval / PESQ, which are
-    not part of this path: driver.py:277-370.)"""
+    improvement; writes up to 10 example utterances.  With `args.bss_eval` (default off) also the BSS-eval figures of the
+    reference's tester (driver.py:297-309) through utils.bss.bss_eval_sources: SDR and SIR improvement -- the metric of the
+    estimates minus the metric of the mixture repeated n_sources times -- and SAR of the estimates, per utterance and as
+    `sdr_improvement`, `sir_improvement`, `sar` of the result.  (The reference additionally calls PESQ, which is not part
+    of this path: driver.py:277-370.)"""
 
     def __init__(self, model, loader, pit_criterion, args):
         self.model, self.loader, self.pit_criterion = model, loader, pit_criterion
@@ -197,6 +200,7 @@ class Tester:
         if self.out_dir:
             os.makedirs(self.out_dir, exist_ok=True)
         self.device = next(model.parameters()).device
+        self.bss_eval = bool(getattr(args, "bss_eval", False))
         if getattr(args, "model_path", None):
             ck = load_checkpoint(args.model_path, getattr(args, "trust_pickle", None))
             model.load_state_dict(ck["state_dict"])
@@ -206,7 +210,10 @@ class Tester:
         self.model.eval()
         n = len(self.loader.dataset)
         tot_loss = tot_imp = tot_sisdri = 0.0
-        print("ID, Loss, Loss improvement, SI-SDR improvement", flush=True)
+        tot_bss = [0.0, 0.0, 0.0]
+        if self.bss_eval:
+            from utils.bss import bss_eval_sources
+        print("ID, Loss, Loss improvement, SI-SDR improvement" + (", SDR improvement, SIR improvement, SAR" if self.bss_eval else ""), flush=True)
         with torch.no_grad():
             for idx, (mixture, sources, ids) in enumerate(DevicePrefetcher(self.loader, self.device)):
                 output = self.model(mixture)
@@ -216,7 +223,13 @@ class Tester:
                 est = output[0][perm[0]]                                  # estimates reordered to the targets' order
                 sisdri = (sisdr(est, sources[0]) - sisdr(rep[0], sources[0])).mean().item()
                 l, lm = loss.sum().item(), loss_mix.sum().item()
-                print("{}, {:.3f}, {:.3f}, {:.3f}".format(ids[0], l, lm - l, sisdri), flush=True)
+                row = "{}, {:.3f}, {:.3f}, {:.3f}".format(ids[0], l, lm - l, sisdri)
+                if self.bss_eval:
+                    scored, scored_mix = bss_eval_sources(sources[0], output[0]), bss_eval_sources(sources[0], rep[0])
+                    bss = [(scored[0] - scored_mix[0]).mean().item(), (scored[1] - scored_mix[1]).mean().item(), scored[2].mean().item()]
+                    tot_bss = [a + b for a, b in zip(tot_bss, bss)]
+                    row += ", {:.3f}, {:.3f}, {:.3f}".format(*bss)
+                print(row, flush=True)
                 tot_loss += l
                 tot_imp += lm - l
                 tot_sisdri += sisdri
@@ -229,5 +242,9 @@ class Tester:
                         write_wav(os.path.join(self.out_dir, "{}_{}-estimated.wav".format(ids[0], k + 1)),
                                   e / e.abs().max().clamp_min(1e-12), self.sample_rate, BITS_PER_SAMPLE_WSJ0)
         res = {"loss": tot_loss / n, "loss_improvement": tot_imp / n, "sisdr_improvement": tot_sisdri / n}
-        print("Loss: {loss:.3f}, loss improvement: {loss_improvement:.3f}, SI-SDR improvement: {sisdr_improvement:.3f}".format(**res))
+        summary = "Loss: {loss:.3f}, loss improvement: {loss_improvement:.3f}, SI-SDR improvement: {sisdr_improvement:.3f}".format(**res)
+        if self.bss_eval:
+            res.update(sdr_improvement=tot_bss[0] / n, sir_improvement=tot_bss[1] / n, sar=tot_bss[2] / n)
+            summary += ", SDR improvement: {sdr_improvement:.3f}, SIR improvement: {sir_improvement:.3f}, SAR: {sar:.3f}".format(**res)
+        print(summary)
         return res

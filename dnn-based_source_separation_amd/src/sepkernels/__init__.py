@@ -232,9 +232,13 @@ SIGNATURES = {
     "sep_online_state_row_bytes": [_I, _I, _L, _I],                  # returns size_t
     "sep_online_state_export": [_vp, _I, _vp, _vp, _I, _vp, _I, _vp, _L, _vp, _I, _vp, _L, _vp],
     "sep_online_state_import": [_vp, _I, _vp, _vp, _I, _vp, _I, _vp, _L, _vp, _I, _vp, _L, _vp],
+    # BSS-eval (ABI 23, additive): lagged correlations and the FIR / energy pass of SDR, SIR, SAR (utils/bss.py holds the solve between them)
+    "sep_bss_scratch_bytes": [_I] * 5,                               # returns size_t
+    "sep_bss_xcorr": [_vp] * 5 + [ctypes.c_size_t] + [_I] * 6 + [_vp],
+    "sep_bss_energies": [_vp] * 7 + [ctypes.c_size_t] + [_I] * 5 + [_vp],
 }
 _RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_last_kernel": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
-             "sep_gln_tokens_ws_bytes": ctypes.c_size_t, "sep_online_state_row_bytes": ctypes.c_size_t}
+             "sep_gln_tokens_ws_bytes": ctypes.c_size_t, "sep_online_state_row_bytes": ctypes.c_size_t, "sep_bss_scratch_bytes": ctypes.c_size_t}
 
 _lib = None
 
@@ -888,6 +892,18 @@ class HipBackend:
         _check(load().sep_online_state_import(_ptr(slots, torch.int32), num_streams, _ptr(frames, torch.int64), _ptr(carry, _f32), carry_len,
                                               _ptr(sums, _f64), sums_len, _ptr(rings, _f32), rings_len, _ptr(tail, _f32), tail_len,
                                               _ptr(blob, torch.uint8), row_pitch, _stream()), "sep_online_state_import")
+
+    # ... BSS-eval: a (B, n, T), c (B, m, T) fp32; lengths (B,) int32 on the device or None; out / scratch fp64 (scratch: bss_scratch_bytes)
+    def bss_scratch_bytes(self, B, n, m, T, flen):
+        return int(load().sep_bss_scratch_bytes(B, n, m, T, flen))
+
+    def bss_xcorr(self, a, c, lengths, out, scratch, B, n, m, T, lag_lo, nlag):
+        _check(load().sep_bss_xcorr(_ptr(a, _f32), _ptr(c, _f32), _ptr(lengths, torch.int32), _ptr(out, _f64), _ptr(scratch, _f64), 8 * scratch.numel(),
+                                    B, n, m, T, lag_lo, nlag, _stream()), "sep_bss_xcorr")
+
+    def bss_energies(self, ref, est, filt_all, filt_one, lengths, out, scratch, B, n, m, T, flen):
+        _check(load().sep_bss_energies(_ptr(ref, _f32), _ptr(est, _f32), _ptr(filt_all, _f64), _ptr(filt_one, _f64), _ptr(lengths, torch.int32),
+                                       _ptr(out, _f64), _ptr(scratch, _f64), 8 * scratch.numel(), B, n, m, T, flen, _stream()), "sep_bss_energies")
 
 
 _backend = HipBackend()

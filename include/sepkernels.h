@@ -733,6 +733,38 @@ int sep_online_state_export(const int32_t* slots, int num_streams, const int64_t
 int sep_online_state_import(const int32_t* slots, int num_streams, int64_t* frames, float* carry, int carry_len, double* sums, int sums_len,
                             float* rings, int64_t rings_len, float* tail, int tail_len, const void* blob, int64_t row_pitch, sep_stream_t stream);
 
+/* ---- BSS-eval v3 ("sources"): SDR, SIR and SAR of the test recipes (ABI 23, additive; csrc/loss.hip) --------------------------------------------
+ * The metric of Vincent et al. 2006 as the reference's testers call it (src/utils/bss.py -> mir_eval.separation.bss_eval_sources,
+ * egs/wsj0-mix/common/src/driver.py:291-309).  For references r_0 .. r_{n-1} and estimates e_0 .. e_{m-1} of T_b samples, all extended by flen - 1
+ * zeros: P_i(e_j) is the least-squares projection of e_j on { r_i delayed by tau, tau = 0 .. flen - 1 }, P_all(e_j) the projection on the delayed
+ * versions of every reference; s_filt = P_i(e_j), e_interf = P_all(e_j) - P_i(e_j), e_artif = e_j - P_all(e_j);
+ * SDR = 10 log10(|s_filt|^2 / |e_interf + e_artif|^2), SIR = 10 log10(|s_filt|^2 / |e_interf|^2), SAR = 10 log10(|s_filt + e_interf|^2 / |e_artif|^2).
+ * The projections solve normal equations whose entries are lagged correlations; that solve ((n flen)^2, a few thousand at most) is the CALLER's
+ * (utils/bss.py: torch.linalg in fp64).  The two O(T flen) passes around it are these entry points, fp64 arithmetic on fp32 audio:
+ *   sep_bss_xcorr          out[b][i][k][l] = sum_t a[b][i][t] c[b][k][t + lag_lo + l], l < nlag, over the t with both indices in [0, T_b); product and
+ *                          sum in fp64.  a (B, n, T), c (B, m, T) fp32 rows of pitch T, out (B, n, m, nlag) fp64.  A lag without overlap
+ *                          (|lag| >= T_b) is exactly 0.  One evaluation of the metric calls it twice: references x references with
+ *                          lag_lo = -(flen - 1), nlag = 2 flen - 1 (the block-Toeplitz matrix G), and references x estimates with lag_lo = 0,
+ *                          nlag = flen (the right-hand sides D).
+ *   sep_bss_energies       ref (B, n, T), est (B, m, T); filt_all (B, m, n, flen): [b][j][k] is the filter on r_k in P_all(e_j); filt_one
+ *                          (B, m, n, flen): [b][j][i] is the filter of P_i(e_j); both fp64.  out (B, m, n, 5) fp64: for the pair (e_j, r_i) the
+ *                          sums over t in [0, T_b + flen - 1) of s_filt^2, e_interf^2, e_artif^2, (e_interf + e_artif)^2, (s_filt + e_interf)^2,
+ *                          in this order.  The projected signals are never stored.
+ *   sep_bss_scratch_bytes  the scratch that all three calls of one evaluation (the two sep_bss_xcorr above and sep_bss_energies) can share; 0 for
+ *                          arguments they would refuse.  A single sep_bss_xcorr needs 8 B n m ceil(T / 2048) nlag bytes, sep_bss_energies
+ *                          40 B n m ceil((T + flen - 1) / 1024).  Not a launch: no stream, no sequence-table entry.
+ * lengths: device memory of B int32, T_b = lengths[b] clamped to [0, T], read when the kernels run; NULL means T_b = T for every row.  Samples at
+ * and beyond T_b are never read.  No atomics: a workgroup owns one time slab of fixed size (2048 / 1024 samples, counted from sample 0) and
+ * writes its partial sums to scratch, a second launch of the same call adds the slabs in ascending order.  So two runs give the same bits, and
+ * a row gives the same bits whatever the pitch T and the rows around it are.  scratch is device memory of scratch_bytes bytes, 8-byte aligned,
+ * checked against the need before anything is launched; its contents are scratch before and after.  All offsets are 64-bit.  B <= 65535,
+ * n m <= 65535, T, flen and the lags within 2^30. */
+size_t sep_bss_scratch_bytes(int B, int n, int m, int T, int flen);
+int sep_bss_xcorr(const float* a, const float* c, const int32_t* lengths, double* out, double* scratch, size_t scratch_bytes, int B, int n, int m,
+                  int T, int lag_lo, int nlag, sep_stream_t stream);
+int sep_bss_energies(const float* ref, const float* est, const double* filt_all, const double* filt_one, const int32_t* lengths, double* out,
+                     double* scratch, size_t scratch_bytes, int B, int n, int m, int T, int flen, sep_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
