@@ -71,6 +71,7 @@ const seq_entry SEQ_TABLE[] = {
     SEQ_FN(sep_unfold_dilated), SEQ_FN(sep_fold_dilated), SEQ_FN(sep_online_unfold_fwd), SEQ_FN(sep_online_unfold_fwd_sel), SEQ_FN(sep_online_unfold_fwd_rag),
     SEQ_FN(sep_online_state_export), SEQ_FN(sep_online_state_import),
     SEQ_FN(sep_bss_xcorr), SEQ_FN(sep_bss_energies),
+    SEQ_FN(sep_mixit_gram), SEQ_FN(sep_mixit_search), SEQ_FN(sep_mixit_bwd),
 };
 constexpr int SEQ_COUNT = (int)(sizeof(SEQ_TABLE) / sizeof(SEQ_TABLE[0]));
 

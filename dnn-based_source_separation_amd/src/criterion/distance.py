@@ -29,10 +29,11 @@ class _RowDiffFn(torch.autograd.Function):
     sq_mean     sum (x-t)^2 / T                     -           2/T
     l2          sqrt(sum (x-t)^2)                   -           1/value
     sdr         10 log10((sum t^2+eps)/(sum (x-t)^2+eps))   -   -20/ln10 / (sum (x-t)^2 + eps)
+    tsnr        10 log10((sum t^2+eps)/(sum (x-t)^2+tau sum t^2+eps))   -   -20/ln10 / (sum (x-t)^2 + tau sum t^2 + eps)
     """
 
     @staticmethod
-    def forward(ctx, x, t, kind, eps):
+    def forward(ctx, x, t, kind, eps, tau=0.0):
         if ctx.needs_input_grad[1]:
             raise NotImplementedError("gradient w.r.t. the target of a distance criterion is not implemented")
         K = sepkernels.backend()
@@ -53,6 +54,10 @@ class _RowDiffFn(torch.autograd.Function):
         elif kind == "sdr":
             val = 10.0 * torch.log10((s_tt + eps) / (s_sq + eps))
             c_sq = (-20.0 / math.log(10.0)) / (s_sq + eps)
+        elif kind == "tsnr":
+            den = s_sq + tau * s_tt + eps
+            val = 10.0 * torch.log10((s_tt + eps) / den)
+            c_sq = (-20.0 / math.log(10.0)) / den
         else:
             raise ValueError("unknown row distance '{}'".format(kind))
         ctx.save_for_backward(x, t, c_abs if c_abs is not None else c_sq)
@@ -70,11 +75,11 @@ class _RowDiffFn(torch.autograd.Function):
             r1 = min(rows, r0 + _MAX_ROWS)
             c = coef[r0:r1]
             K.rowdiff_bwd(x[r0:r1], t[r0:r1], c if ctx.is_abs else None, None if ctx.is_abs else c, dx[r0:r1], r1 - r0, T)
-        return dx, None, None, None
+        return dx, None, None, None, None
 
 
-def row_distance(input, target, dim, kind, eps=EPS):
-    """Reduce `kind` of (input, target) over `dim` (int or tuple of ints); returns the remaining axes."""
+def row_distance(input, target, dim, kind, eps=EPS, tau=0.0):
+    """Reduce `kind` of (input, target) over `dim` (int or tuple of ints); returns the remaining axes.  `tau` is read by kind "tsnr" only."""
     dims = (dim,) if isinstance(dim, int) else tuple(dim)
     dims = tuple(sorted(d % input.dim() for d in dims))
     if input.dtype != torch.float32 and sepkernels.backend().name == "hip":
@@ -88,7 +93,7 @@ def row_distance(input, target, dim, kind, eps=EPS):
     for d in last:
         T *= input.shape[d]
     rows = input.numel() // T
-    out = _RowDiffFn.apply(input.reshape(rows, T).contiguous(), target.reshape(rows, T).contiguous(), kind, eps)
+    out = _RowDiffFn.apply(input.reshape(rows, T).contiguous(), target.reshape(rows, T).contiguous(), kind, eps, tau)
     return out.view(lead)
 
 

@@ -1,6 +1,7 @@
 """
 SDR and scale-invariant SDR on MI355X.  API of reference src/criterion/sdr.py:6-231 (`sdr`, `SDR`, `NegSDR`, `sisdr`,
-`SISDR`, `NegSISDR` with `reduction`, `eps`, `forward(input, target, batch_mean=True)`, `.maximize`).
+`SISDR`, `NegSISDR` with `reduction`, `eps`, `forward(input, target, batch_mean=True)`, `.maximize`), plus the thresholded SNR of the
+MixIT paper (`thresholded_snr`, `ThresholdedSNR`, `NegThresholdedSNR`), which the reference does not have.
 
 The O(T) work is two kernels of libsepkernels: sep_sisdr_dots (the three dot products per pair, fp64
 accumulation) and sep_sisdr_bwd (analytic gradient applied elementwise); the value itself is formed from the
@@ -113,7 +114,32 @@ def sdr(input, target, eps=EPS):
     from criterion.distance import row_distance
     n_dims = input.dim()
     assert n_dims in [2, 3, 4], "Only 2D or 3D or 4D tensor is acceptable, but given {}D tensor.".format(n_dims)
+    if _on_host(input):
+        return _snr_aten(input, target.to(input.dtype), 0.0, eps)
     return row_distance(input, target, n_dims - 1, "sdr", eps=eps)
+
+
+def _snr_aten(input, target, tau, eps):
+    tt = target.square().sum(-1)
+    return 10 * torch.log10((tt + eps) / ((target - input).square().sum(-1) + tau * tt + eps))
+
+
+def thresholded_snr(input, target, snr_max=30.0, eps=EPS):
+    """
+    The loss of "Unsupervised Sound Separation Using Mixture Invariant Training" (Wisdom et al., 2020), as a measure in dB:
+    Args:
+        input, target: (batch_size, T) or (batch_size, n_sources, T) or (batch_size, n_sources, n_mics, T)
+    Returns:
+        10 log10((|target|^2 + eps) / (|target - input|^2 + tau |target|^2 + eps)) over the last axis with tau = 10^(-snr_max / 10): an SNR that
+        saturates at snr_max dB, so that an estimate already that good stops pulling on the gradient.  Shape input.shape[:-1]
+    """
+    from criterion.distance import row_distance
+    n_dims = input.dim()
+    assert n_dims in [2, 3, 4], "Only 2D or 3D or 4D tensor is acceptable, but given {}D tensor.".format(n_dims)
+    tau = 10.0 ** (-snr_max / 10.0)
+    if _on_host(input):
+        return _snr_aten(input, target.to(input.dtype), tau, eps)
+    return row_distance(input, target, n_dims - 1, "tsnr", eps=eps, tau=tau)
 
 
 class _SISDRBase(nn.Module):
@@ -172,6 +198,35 @@ class SDR(_SISDRBase):
 class NegSDR(_SISDRBase):
     _sign = -1.0
     _measure = staticmethod(lambda input, target, eps: sdr(input, target, eps=eps))
+
+    @property
+    def maximize(self):
+        return False
+
+
+class ThresholdedSNR(_SISDRBase):
+    """SNR that saturates at `snr_max` dB (thresholded_snr above), reduced over the sources like the other measures"""
+    _sign = 1.0
+
+    def __init__(self, snr_max=30.0, reduction="mean", eps=EPS):
+        super().__init__(reduction=reduction, eps=eps)
+        self.snr_max = snr_max
+
+    @property
+    def tau(self):
+        return 10.0 ** (-self.snr_max / 10.0)
+
+    def _measure(self, input, target, eps):
+        return thresholded_snr(input, target, snr_max=self.snr_max, eps=eps)
+
+    @property
+    def maximize(self):
+        return True
+
+
+class NegThresholdedSNR(ThresholdedSNR):
+    """the loss of the MixIT paper: -thresholded SNR, to be minimised"""
+    _sign = -1.0
 
     @property
     def maximize(self):

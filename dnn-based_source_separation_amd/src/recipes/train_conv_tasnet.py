@@ -6,6 +6,11 @@ Command-line trainer for Conv-TasNet on wsj0-mix style data, single- or multi-GP
 
 Option names and defaults follow the reference's egs/wsj0-mix/conv-tasnet/local/train.py:21-66 and train.sh:28-59
 (paper-best model, Adam 1e-3, clip 5, PIT over SI-SDR, 4-s segments at 8 kHz).
+
+`--criterion mixit` trains without isolated sources (mixture invariant training, criterion/mixit.py): every item is the sum of
+`--n_mixtures` mixtures of the list (recipes.wsj0mix.MixtureOfMixtures, re-paired every epoch), the model emits `--n_sources` estimates and
+the loss is the best way to hand them back to the mixtures under `--mixit_measure` (snr: the thresholded SNR of the MixIT paper, 30 dB;
+sisdr: negative SI-SDR).  Validation scores mixtures of mixtures of the validation list with the same criterion.
 """
 import argparse
 import os
@@ -18,7 +23,7 @@ from criterion.sdr import NegSISDR
 from models.conv_tasnet import ConvTasNet
 
 from .trainer import Trainer
-from .wsj0mix import EvalDataLoader, TrainDataLoader, WaveEvalDataset, WaveTrainDataset, shard_for_rank
+from .wsj0mix import EvalDataLoader, MixtureOfMixtures, TrainDataLoader, WaveEvalDataset, WaveTrainDataset, shard_for_rank
 
 
 def _flag(v):
@@ -53,7 +58,9 @@ def build_parser():
     ap.add_argument("--sep_norm", type=_flag, default=True)
     ap.add_argument("--mask_nonlinear", default="sigmoid")
     ap.add_argument("--n_sources", type=int, default=2)
-    ap.add_argument("--criterion", default="sisdr", choices=["sisdr"])
+    ap.add_argument("--criterion", default="sisdr", choices=["sisdr", "mixit"])
+    ap.add_argument("--mixit_measure", default="snr", choices=["sisdr", "snr"], help="with --criterion mixit: what scores a remix against its mixture")
+    ap.add_argument("--n_mixtures", type=int, default=2, help="with --criterion mixit: reference mixtures summed into one training item")
     ap.add_argument("--optimizer", default="adam", choices=["adam"])
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--weight_decay", type=float, default=0.0)
@@ -68,6 +75,15 @@ def build_parser():
     ap.add_argument("--num_workers", type=int, default=2)
     ap.add_argument("--seed", type=int, default=111)
     return ap
+
+
+def build_criterion(args):
+    """--criterion sisdr: PIT over negative SI-SDR; --criterion mixit: MixIT over --mixit_measure (--n_sources is then the number of estimates)"""
+    if args.criterion == "mixit":
+        from criterion.mixit import MixIT
+        from criterion.sdr import NegThresholdedSNR
+        return MixIT(NegThresholdedSNR(snr_max=30.0) if args.mixit_measure == "snr" else NegSISDR())
+    return PIT1d(NegSISDR(), n_sources=args.n_sources)
 
 
 def main(argv=None):
@@ -88,15 +104,21 @@ def main(argv=None):
     samples = int(args.sample_rate * args.duration)
     train_set = WaveTrainDataset(args.train_wav_root, args.train_list_path, samples=samples, overlap=samples // 2, n_sources=args.n_sources)
     valid_set = WaveEvalDataset(args.valid_wav_root, args.valid_list_path, max_samples=int(args.sample_rate * args.valid_duration), n_sources=args.n_sources)
+    mixit = args.criterion == "mixit"
+    if mixit:       # the list's isolated sources are never read: items are sums of --n_mixtures of its mixtures
+        train_set = MixtureOfMixtures(train_set, n_mixtures=args.n_mixtures, seed=args.seed)
+        valid_set = MixtureOfMixtures(valid_set, n_mixtures=args.n_mixtures, seed=args.seed)
     if rank == 0:
         print("Training dataset includes {} samples.".format(len(train_set)))
         print("Valid dataset includes {} samples.".format(len(valid_set)))
     def train_loader(epoch):
+        if mixit:
+            train_set.set_epoch(epoch)
         shard = shard_for_rank(train_set, rank, world, seed=args.seed, epoch=epoch) if world > 1 else train_set
         return TrainDataLoader(shard, batch_size=args.batch_size, shuffle=True, drop_last=True, num_workers=args.num_workers)
 
     loader = {"train": train_loader(0), "valid": EvalDataLoader(valid_set, batch_size=1, shuffle=False)}
-    args.reshard = train_loader if world > 1 else None      # every rank trains on a different subset each epoch
+    args.reshard = train_loader if world > 1 or mixit else None      # every rank trains on a different subset each epoch; MixIT re-pairs
 
     stride = args.kernel_size // 2 if args.stride is None else args.stride
     model = ConvTasNet(args.n_basis, args.kernel_size, stride=stride, enc_basis=args.enc_basis, dec_basis=args.dec_basis,
@@ -108,7 +130,7 @@ def main(argv=None):
     if rank == 0:
         print(model)
         print("# Parameters: {}".format(model.num_parameters), flush=True)
-    trainer = Trainer(model, loader, PIT1d(NegSISDR(), n_sources=args.n_sources), args)
+    trainer = Trainer(model, loader, build_criterion(args), args)
     trainer.run()
     if world > 1:
         dist.destroy_process_group()

@@ -8,6 +8,8 @@ Directory contract (same as the reference, egs/wsj0-mix/common/src/dataset.py:13
                     (overlap defaults to samples // 2), incomplete tail windows dropped  -> (mixture (1,T), sources (n,T))
 * WaveEvalDataset   one item per utterance, cut to `max_samples`                        -> (+ ID)
 * WaveTestDataset   same items, for the tester                                          -> (+ ID)
+* MixtureOfMixtures wraps one of the above for mixture invariant training: item i is the mixture of item i and of n_mixtures - 1
+                    partners, cut to the shortest                                       -> (sum of mixtures (1,T), mixtures (N,T)[, ID])
 * TrainDataLoader / EvalDataLoader / TestDataLoader   thin DataLoader subclasses (eval / test insist on batch_size 1,
                     utterances have different lengths)
 * DevicePrefetcher  wraps a loader: pinned staging + asynchronous H2D on a copy stream, one batch ahead, so the fused
@@ -81,6 +83,48 @@ class WaveEvalDataset(_WaveItems):
 
 class WaveTestDataset(WaveEvalDataset):
     pass
+
+
+class MixtureOfMixtures(Dataset):
+    """Items for mixture invariant training (criterion.mixit): item i pairs mixture i of the wrapped dataset with `n_mixtures` - 1 other ones,
+    all cut to the shortest, and yields (their sum (1, T), the mixtures (n_mixtures, T)) -- plus the first one's ID when the wrapped items
+    carry IDs.  The partners of item i are drawn by a generator seeded with (seed, epoch, i): call set_epoch(epoch) before every pass over a
+    training set and the pairing changes with the epoch; leave it alone and the pairing is fixed (validation sets).  Only the mixtures are
+    read: the wrapped dataset's isolated sources are never opened, which is the point of the method."""
+
+    def __init__(self, dataset, n_mixtures=2, seed=0):
+        super().__init__()
+        if n_mixtures < 1 or (n_mixtures > 1 and len(dataset) < n_mixtures):
+            raise ValueError("{} mixtures per item need a dataset of at least as many items (it has {})".format(n_mixtures, len(dataset)))
+        self.dataset, self.n_mixtures, self.seed, self.epoch = dataset, n_mixtures, seed, 0
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def partners(self, idx):
+        """indices of the n_mixtures - 1 other items mixed into item idx: distinct, none of them idx"""
+        g = torch.Generator().manual_seed(((self.seed * 1000003 + self.epoch) * 1000003 + idx) % (1 << 63))
+        others = torch.randperm(len(self.dataset) - 1, generator=g)[:self.n_mixtures - 1]
+        return [int(o) + (int(o) >= idx) for o in others]
+
+    def _mixture(self, idx):
+        """(mixture (1, T), ID or None) of one wrapped item without touching its sources where the dataset can say how (wsj0-mix trees)"""
+        ds = self.dataset
+        if hasattr(ds, "items") and hasattr(ds, "_path"):
+            ID, start, end = ds.items[idx]
+            return read_wav(ds._path("mix", ID), start, end - start)[0], (ID if isinstance(ds, WaveEvalDataset) else None)
+        item = ds[idx]
+        return item[0], (item[2] if len(item) > 2 else None)
+
+    def __getitem__(self, idx):
+        got = [self._mixture(i) for i in [idx] + self.partners(idx)]
+        T = min(m.shape[-1] for m, _ in got)
+        mixtures = torch.cat([m[..., :T].reshape(-1, T)[:1] for m, _ in got], dim=0)
+        out = (mixtures.sum(dim=0, keepdim=True), mixtures)
+        return out if got[0][1] is None else out + (got[0][1],)
 
 
 class TrainDataLoader(DataLoader):

@@ -22,6 +22,8 @@ LSTM_INTERLEAVED = 0x400       # sep_lstm_fwd / sep_lstm_bwd with reverse = 2: h
 STATS_SLOTS = 16   # SEP_STATS_SLOTS: gLN statistics are double[B][STATS_SLOTS][2]
 ARRIVE_INTS = 17   # SEP_ARRIVE_INTS: arrival counters of the gLN-backward publishers, int[B][ARRIVE_INTS]
 ARITH_F32, ARITH_BF16X6, ARITH_F16X3 = 0, 1, 2     # SEP_ARITH_*: how sep_pw_gemm forms its fp32 products (include/sepkernels.h)
+MIXIT_SLAB = 2048  # SEP_MIXIT_SLAB: samples behind one partial sum of sep_mixit_gram
+MIXIT_MAX_EST, MIXIT_MAX_MIX, MIXIT_MAX_CODES = 16, 8, 65536       # SEP_MIXIT_MAX_*: what sep_mixit_search takes
 _ARITH_NAMES = {"f32": ARITH_F32, "bf16x6": ARITH_BF16X6, "f16x3": ARITH_F16X3}
 _gemm_arith = None
 
@@ -236,9 +238,15 @@ SIGNATURES = {
     "sep_bss_scratch_bytes": [_I] * 5,                               # returns size_t
     "sep_bss_xcorr": [_vp] * 5 + [ctypes.c_size_t] + [_I] * 6 + [_vp],
     "sep_bss_energies": [_vp] * 7 + [ctypes.c_size_t] + [_I] * 5 + [_vp],
+    # mixture invariant training (ABI 23, additive): the Gram matrix of estimates and mixtures, the search over the N^M assignments, the gradient
+    "sep_mixit_scratch_bytes": [_I] * 4,                             # returns size_t
+    "sep_mixit_gram": [_vp] * 4 + [ctypes.c_size_t] + [_I] * 4 + [_vp],
+    "sep_mixit_search": [_vp] + [_I] * 6 + [_D, _D] + [_vp] * 3 + [_vp],
+    "sep_mixit_bwd": [_vp] * 6 + [_I] * 5 + [_D, _D] + [_vp],
 }
 _RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_last_kernel": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
-             "sep_gln_tokens_ws_bytes": ctypes.c_size_t, "sep_online_state_row_bytes": ctypes.c_size_t, "sep_bss_scratch_bytes": ctypes.c_size_t}
+             "sep_gln_tokens_ws_bytes": ctypes.c_size_t, "sep_online_state_row_bytes": ctypes.c_size_t, "sep_bss_scratch_bytes": ctypes.c_size_t,
+             "sep_mixit_scratch_bytes": ctypes.c_size_t}
 
 _lib = None
 
@@ -904,6 +912,23 @@ class HipBackend:
     def bss_energies(self, ref, est, filt_all, filt_one, lengths, out, scratch, B, n, m, T, flen):
         _check(load().sep_bss_energies(_ptr(ref, _f32), _ptr(est, _f32), _ptr(filt_all, _f64), _ptr(filt_one, _f64), _ptr(lengths, torch.int32),
                                        _ptr(out, _f64), _ptr(scratch, _f64), 8 * scratch.numel(), B, n, m, T, flen, _stream()), "sep_bss_energies")
+
+    # ... mixture invariant training: est (B, M, T), tgt (B, N, T) fp32; gram (B, M + N, M + N) and scratch fp64 (scratch: mixit_scratch_bytes);
+    # kind 0 SI-SDR, 1 SDR, 2 thresholded SNR; gw (B,) fp32 arrives at every per-mixture measure of an item (a mean's 1 / N folded in)
+    def mixit_scratch_bytes(self, B, M, N, T):
+        return int(load().sep_mixit_scratch_bytes(B, M, N, T))
+
+    def mixit_gram(self, est, tgt, gram, scratch, B, M, N, T):
+        _check(load().sep_mixit_gram(_ptr(est, _f32), _ptr(tgt, _f32), _ptr(gram, _f64), _ptr(scratch, _f64), 8 * scratch.numel(), B, M, N, T, _stream()),
+               "sep_mixit_gram")
+
+    def mixit_search(self, gram, B, M, N, kind, maximize, use_mean, eps, tau, best_val, best_idx, per_mix):
+        _check(load().sep_mixit_search(_ptr(gram, _f64), B, M, N, kind, int(maximize), int(use_mean), eps, tau, _ptr(best_val, _f32),
+                                       _ptr(best_idx, torch.int64), _ptr(per_mix, _f32), _stream()), "sep_mixit_search")
+
+    def mixit_bwd(self, est, tgt, gram, best_idx, gw, d_est, B, M, N, T, kind, eps, tau):
+        _check(load().sep_mixit_bwd(_ptr(est, _f32), _ptr(tgt, _f32), _ptr(gram, _f64), _ptr(best_idx, torch.int64), _ptr(gw, _f32), _ptr(d_est, _f32),
+                                    B, M, N, T, kind, eps, tau, _stream()), "sep_mixit_bwd")
 
 
 _backend = HipBackend()

@@ -765,6 +765,43 @@ int sep_bss_xcorr(const float* a, const float* c, const int32_t* lengths, double
 int sep_bss_energies(const float* ref, const float* est, const double* filt_all, const double* filt_one, const int32_t* lengths, double* out,
                      double* scratch, size_t scratch_bytes, int B, int n, int m, int T, int flen, sep_stream_t stream);
 
+/* ---- Mixture invariant training (MixIT, Wisdom et al. 2020; ABI 23, additive; csrc/loss.hip, criterion/mixit.py) ---------------------------------
+ * M estimates est (B, M, T) of the sum of N reference mixtures tgt (B, N, T), fp32 rows of pitch T.  An assignment hands every estimate to exactly
+ * one mixture; its code is sum_m n(m) N^(M-1-m) (itertools.product(range(N), repeat=M) order, estimate 0 most significant).  The remix of
+ * mixture n is y_n = sum of the estimates with n(m) = n (zero for an empty set), and the measure of (y_n, x_n) is a function of three inner
+ * products, each a sum of entries of ONE Gram matrix of the R = M + N rows (estimates first):
+ *     tt = G[M+n][M+n],   a = sum_{m in set n} G[M+n][m],   yy = sum_{m, m' in set n} G[m][m'].
+ *   kind 0 (SI-SDR)           alpha = a / (tt + eps);  10 log10((alpha^2 tt + eps) / (max(alpha^2 tt - 2 alpha a + yy, 0) + eps))
+ *   kind 1 (SDR)              10 log10((tt + eps) / (max(tt - 2 a + yy, 0) + eps))
+ *   kind 2 (thresholded SNR)  10 log10((tt + eps) / (max(tt - 2 a + yy, 0) + tau tt + eps))
+ * 1 <= M <= 16, 1 <= N <= 8, N^M <= 65536, B <= 65535, T <= 2^30.
+ *   sep_mixit_gram           gram (B, R, R) fp64: G[i][j] = sum_t row_i[t] row_j[t], product and sum in fp64 (the product of two fp32 values is
+ *                            exact there).  Both triangles are written, bit for bit symmetric; no entry keeps what it held.  ONE pass over the
+ *                            rows for R <= 12 (a workgroup owns SEP_MIXIT_SLAB samples of all R rows of an item, a thread holds the R values of a
+ *                            sample and forms the R (R + 1) / 2 products); beyond that 8 x 8 blocks of the matrix per workgroup.  No atomics: the
+ *                            slab partials go to scratch and a second launch of the same call adds them in ascending order, so two runs give the
+ *                            same bits and an item gives the same bits in any batch.
+ *   sep_mixit_scratch_bytes  8 B ceil(T / SEP_MIXIT_SLAB) R^2, or 0 for arguments sep_mixit_gram would refuse.  Not a launch.
+ *   sep_mixit_search         one workgroup per item strides over the N^M codes, evaluates the measure of every mixture in fp64 from gram, reduces
+ *                            over the mixtures by mean (use_mean) or sum and keeps the maximum (maximize) or minimum; the lowest code wins a tie
+ *                            (torch.max / torch.min).  best_val (B) fp32, best_idx (B) int64: the code, per_mix (B, N) fp32: the measure of every
+ *                            mixture at that code.
+ *   sep_mixit_bwd            d_est[b][m][t] = gw[b] (cT_n x_n[t] + cE_n y_n[t]) with n = n(m) under the code best_idx[b], where
+ *                            cT_n x_n + cE_n y_n = d measure_n / d y_n.  gw (B) fp32 is the gradient that arrives at EVERY per-mixture measure of
+ *                            item b: the caller folds the 1 / N of a mean over the mixtures (and any sign) into it.  One read of the R rows, one
+ *                            write of the M rows; every element of d_est is written.  A best_idx outside [0, 65536) is read as code 0. */
+#define SEP_MIXIT_SLAB 2048
+#define SEP_MIXIT_MAX_EST 16
+#define SEP_MIXIT_MAX_MIX 8
+#define SEP_MIXIT_MAX_CODES 65536
+size_t sep_mixit_scratch_bytes(int B, int M, int N, int T);
+int sep_mixit_gram(const float* est, const float* tgt, double* gram, double* scratch, size_t scratch_bytes, int B, int M, int N, int T,
+                   sep_stream_t stream);
+int sep_mixit_search(const double* gram, int B, int M, int N, int kind, int maximize, int use_mean, double eps, double tau, float* best_val,
+                     int64_t* best_idx, float* per_mix, sep_stream_t stream);
+int sep_mixit_bwd(const float* est, const float* tgt, const double* gram, const int64_t* best_idx, const float* gw, float* d_est, int B, int M,
+                  int N, int T, int kind, double eps, double tau, sep_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
