@@ -72,6 +72,7 @@ const seq_entry SEQ_TABLE[] = {
     SEQ_FN(sep_online_state_export), SEQ_FN(sep_online_state_import),
     SEQ_FN(sep_bss_xcorr), SEQ_FN(sep_bss_energies),
     SEQ_FN(sep_mixit_gram), SEQ_FN(sep_mixit_search), SEQ_FN(sep_mixit_bwd),
+    SEQ_FN(sep_pair_gram), SEQ_FN(sep_assign), SEQ_FN(sep_pair_assign), SEQ_FN(sep_pair_bwd),
 };
 constexpr int SEQ_COUNT = (int)(sizeof(SEQ_TABLE) / sizeof(SEQ_TABLE[0]));
 

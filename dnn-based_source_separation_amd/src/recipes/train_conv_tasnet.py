@@ -11,6 +11,10 @@ Option names and defaults follow the reference's egs/wsj0-mix/conv-tasnet/local/
 `--n_mixtures` mixtures of the list (recipes.wsj0mix.MixtureOfMixtures, re-paired every epoch), the model emits `--n_sources` estimates and
 the loss is the best way to hand them back to the mixtures under `--mixit_measure` (snr: the thresholded SNR of the MixIT paper, 30 dB;
 sisdr: negative SI-SDR).  Validation scores mixtures of mixtures of the validation list with the same criterion.
+
+`--criterion hungarian` trains on isolated sources like `sisdr`, with the best permutation found as an O(n^3) assignment problem
+(criterion/hungarian.py) instead of PIT's table of n! permutations: any `--n_sources`.  `--hungarian_measure` picks what scores a pair
+(sisdr: negative SI-SDR; snr: the thresholded SNR, 30 dB).  Validation uses the same criterion.
 """
 import argparse
 import os
@@ -58,7 +62,8 @@ def build_parser():
     ap.add_argument("--sep_norm", type=_flag, default=True)
     ap.add_argument("--mask_nonlinear", default="sigmoid")
     ap.add_argument("--n_sources", type=int, default=2)
-    ap.add_argument("--criterion", default="sisdr", choices=["sisdr", "mixit"])
+    ap.add_argument("--criterion", default="sisdr", choices=["sisdr", "mixit", "hungarian"])
+    ap.add_argument("--hungarian_measure", default="sisdr", choices=["sisdr", "snr"], help="with --criterion hungarian: what scores an estimate against a target")
     ap.add_argument("--mixit_measure", default="snr", choices=["sisdr", "snr"], help="with --criterion mixit: what scores a remix against its mixture")
     ap.add_argument("--n_mixtures", type=int, default=2, help="with --criterion mixit: reference mixtures summed into one training item")
     ap.add_argument("--optimizer", default="adam", choices=["adam"])
@@ -78,7 +83,12 @@ def build_parser():
 
 
 def build_criterion(args):
-    """--criterion sisdr: PIT over negative SI-SDR; --criterion mixit: MixIT over --mixit_measure (--n_sources is then the number of estimates)"""
+    """--criterion sisdr: PIT over negative SI-SDR; --criterion mixit: MixIT over --mixit_measure (--n_sources is then the number of estimates);
+    --criterion hungarian: the optimal permutation by assignment over --hungarian_measure, for any --n_sources"""
+    if args.criterion == "hungarian":
+        from criterion.hungarian import HungarianLoss
+        from criterion.sdr import NegThresholdedSNR
+        return HungarianLoss(NegThresholdedSNR(snr_max=30.0) if args.hungarian_measure == "snr" else NegSISDR())
     if args.criterion == "mixit":
         from criterion.mixit import MixIT
         from criterion.sdr import NegThresholdedSNR

@@ -24,6 +24,8 @@ ARRIVE_INTS = 17   # SEP_ARRIVE_INTS: arrival counters of the gLN-backward publi
 ARITH_F32, ARITH_BF16X6, ARITH_F16X3 = 0, 1, 2     # SEP_ARITH_*: how sep_pw_gemm forms its fp32 products (include/sepkernels.h)
 MIXIT_SLAB = 2048  # SEP_MIXIT_SLAB: samples behind one partial sum of sep_mixit_gram
 MIXIT_MAX_EST, MIXIT_MAX_MIX, MIXIT_MAX_CODES = 16, 8, 65536       # SEP_MIXIT_MAX_*: what sep_mixit_search takes
+PAIR_SLAB = 2048   # SEP_PAIR_SLAB: samples behind one partial sum of sep_pair_gram
+ASSIGN_MAX_N = 64   # SEP_ASSIGN_MAX_N: the largest matrix sep_assign / sep_pair_assign take (a column per lane of a wavefront)
 _ARITH_NAMES = {"f32": ARITH_F32, "bf16x6": ARITH_BF16X6, "f16x3": ARITH_F16X3}
 _gemm_arith = None
 
@@ -243,10 +245,16 @@ SIGNATURES = {
     "sep_mixit_gram": [_vp] * 4 + [ctypes.c_size_t] + [_I] * 4 + [_vp],
     "sep_mixit_search": [_vp] + [_I] * 6 + [_D, _D] + [_vp] * 3 + [_vp],
     "sep_mixit_bwd": [_vp] * 6 + [_I] * 5 + [_D, _D] + [_vp],
+    # optimal-permutation (Hungarian) training (ABI 23, additive): the pair inner products in one pass, the O(n^3) assignment, the gradient
+    "sep_pair_gram_scratch_bytes": [_I] * 3,                         # returns size_t
+    "sep_pair_gram": [_vp] * 6 + [ctypes.c_size_t] + [_I] * 3 + [_vp],
+    "sep_assign": [_vp] + [_I] * 3 + [_vp] * 3 + [_vp],
+    "sep_pair_assign": [_vp] * 3 + [_I] * 5 + [_D, _D] + [_vp] * 4 + [_vp],
+    "sep_pair_bwd": [_vp] * 8 + [_I] * 4 + [_D, _D] + [_vp],
 }
 _RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_last_kernel": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
              "sep_gln_tokens_ws_bytes": ctypes.c_size_t, "sep_online_state_row_bytes": ctypes.c_size_t, "sep_bss_scratch_bytes": ctypes.c_size_t,
-             "sep_mixit_scratch_bytes": ctypes.c_size_t}
+             "sep_mixit_scratch_bytes": ctypes.c_size_t, "sep_pair_gram_scratch_bytes": ctypes.c_size_t}
 
 _lib = None
 
@@ -929,6 +937,26 @@ class HipBackend:
     def mixit_bwd(self, est, tgt, gram, best_idx, gw, d_est, B, M, N, T, kind, eps, tau):
         _check(load().sep_mixit_bwd(_ptr(est, _f32), _ptr(tgt, _f32), _ptr(gram, _f64), _ptr(best_idx, torch.int64), _ptr(gw, _f32), _ptr(d_est, _f32),
                                     B, M, N, T, kind, eps, tau, _stream()), "sep_mixit_bwd")
+
+    # ... optimal-permutation training: est, tgt (B, n, T) fp32; dots (B, n, n), tt, xx (B, n) and scratch fp64 (scratch: pair_gram_scratch_bytes);
+    # perm (B, n) int64: the target of every estimate; duals (B, 2 n) fp64 or None (pair_assign); kind and gw as for MixIT
+    def pair_gram_scratch_bytes(self, B, n, T):
+        return int(load().sep_pair_gram_scratch_bytes(B, n, T))
+
+    def pair_gram(self, est, tgt, dots, tt, xx, scratch, B, n, T):
+        _check(load().sep_pair_gram(_ptr(est, _f32), _ptr(tgt, _f32), _ptr(dots, _f64), _ptr(tt, _f64), _ptr(xx, _f64), _ptr(scratch, _f64), 8 * scratch.numel(),
+                                    B, n, T, _stream()), "sep_pair_gram")
+
+    def assign(self, cost, B, n, maximize, perm, total, duals):
+        _check(load().sep_assign(_ptr(cost, _f64), B, n, int(maximize), _ptr(perm, torch.int64), _ptr(total, _f64), _ptr(duals, _f64), _stream()), "sep_assign")
+
+    def pair_assign(self, dots, tt, xx, B, n, kind, maximize, use_mean, eps, tau, best_val, perm, per_src, duals=None):
+        _check(load().sep_pair_assign(_ptr(dots, _f64), _ptr(tt, _f64), _ptr(xx, _f64), B, n, kind, int(maximize), int(use_mean), eps, tau, _ptr(best_val, _f32),
+                                      _ptr(perm, torch.int64), _ptr(per_src, _f32), _ptr(duals, _f64), _stream()), "sep_pair_assign")
+
+    def pair_bwd(self, est, tgt, dots, tt, xx, perm, gw, d_est, B, n, T, kind, eps, tau):
+        _check(load().sep_pair_bwd(_ptr(est, _f32), _ptr(tgt, _f32), _ptr(dots, _f64), _ptr(tt, _f64), _ptr(xx, _f64), _ptr(perm, torch.int64), _ptr(gw, _f32),
+                                   _ptr(d_est, _f32), B, n, T, kind, eps, tau, _stream()), "sep_pair_bwd")
 
 
 _backend = HipBackend()

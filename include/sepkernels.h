@@ -802,6 +802,53 @@ int sep_mixit_search(const double* gram, int B, int M, int N, int kind, int maxi
 int sep_mixit_bwd(const float* est, const float* tgt, const double* gram, const int64_t* best_idx, const float* gw, float* d_est, int B, int M,
                   int N, int T, int kind, double eps, double tau, sep_stream_t stream);
 
+/* ---- Optimal-permutation (Hungarian) training (Dovrat, Nachmani, Wolf 2021; ABI 23, additive; csrc/loss.hip, criterion/hungarian.py) --------------
+ * n estimates est (B, n, T) of n targets tgt (B, n, T), fp32 rows of pitch T.  The loss is the best of the n! ways to pair them, found as a linear
+ * assignment problem on the n x n matrix of pair measures in O(n^3), not by a table of permutations.  1 <= n <= SEP_ASSIGN_MAX_N = 64 (a column
+ * per lane of one wavefront), B <= 65535 for the calls that walk the waveforms, T >= 1.  Anything else is refused with a message before any launch.
+ *   sep_pair_gram            dots (B, n, n): dots[b][i][j] = <est_i, tgt_j>, tt (B, n): |tgt_j|^2, xx (B, n): |est_i|^2, all fp64, product and sum
+ *                            in fp64 (the product of two fp32 values is exact there): the layout sep_sisdr_dots fills with all_pairs = 1, so
+ *                            sep_sisdr_from_dots and sep_sisdr_bwd take them.  The outputs are WRITTEN, not accumulated: no zeroing.  ONE pass: a
+ *                            workgroup owns SEP_PAIR_SLAB samples of an 8 x 8 block of (estimate, target) pairs in fp64 registers (4 x 4 for
+ *                            n <= 4), so a sample is read ceil(n / 8) times per side -- sep_sisdr_dots reads it n times.  No atomics: per thread in
+ *                            ascending time, a wave butterfly, the four waves in order, the slab partials to scratch, a second launch of the same
+ *                            call adds them in ascending slab order.  Two runs give the same bits; an item gives the same bits in any batch.
+ *   sep_pair_gram_scratch_bytes  8 B ceil(T / SEP_PAIR_SLAB) (n^2 + 2 n), or 0 for arguments sep_pair_gram would refuse.  Not a launch.
+ *   sep_assign               cost (B, n, n) fp64 -> perm (B, n) int64: row i is matched to column perm[i]; total (B) fp64: sum_i cost[i][perm[i]]
+ *                            added in ascending i; duals (B, 2 n) fp64: row potentials u, then column potentials v.  The exact minimum-cost
+ *                            perfect matching, or the maximum-cost one if `maximize`: the costs are then negated on entry (total is the sum of the
+ *                            costs as given) and duals are those of the negated, i.e. minimisation, problem: u_i + v_j <= c_ij for every pair
+ *                            and sum u + sum v = sum_i c[i][perm[i]] in exact arithmetic -- a certificate of optimality.  Shortest augmenting
+ *                            paths with potentials (Jonker-Volgenant, the O(n^3) Hungarian method), one wavefront per item, the matrix in 32 KB
+ *                            of LDS, lane j owns column j; the next column is the unused one of least reduced cost by a wave reduction on
+ *                            (value, column) pairs, the lowest column among equals.  TIES: any optimal assignment is a correct answer; the call
+ *                            returns the same one every time for the same bits, the one this search order reaches -- NOT "the first in
+ *                            itertools.permutations order" of sep_pit_search.  NON-FINITE costs: every loop has a trip count fixed by n (n rows,
+ *                            at most n + 1 columns per augmentation, at most n steps back along the path) and a column whose value does not
+ *                            compare is offered as +inf, the lowest unused column taken if nothing compares: NaN and +-Inf give SOME valid
+ *                            permutation and whatever total the arithmetic gives; the call never spins and never indexes out of range.
+ *   sep_pair_assign          the same solver on the matrix of pair measures m[i][j] formed in fp64 from (dots[i][j], tt[j], xx[i]) -- in dB, not
+ *                            negated; `maximize` picks the sense, the caller maps a negated loss onto it:
+ *                              kind 0 (SI-SDR)           alpha = a / (tt + eps);  10 log10((alpha^2 tt + eps) / (max(alpha^2 tt - 2 alpha a + xx, 0) + eps))
+ *                              kind 1 (SDR)              10 log10((tt + eps) / (max(tt - 2 a + xx, 0) + eps))
+ *                              kind 2 (thresholded SNR)  10 log10((tt + eps) / (max(tt - 2 a + xx, 0) + tau tt + eps))
+ *                            best_val (B) fp32: the sum, or the mean if use_mean, of m[i][perm[i]] added in ascending i in fp64; perm (B, n) int64;
+ *                            per_src (B, n) fp32: m[i][perm[i]]; duals (B, 2 n) as above, of the matrix the solver saw (-m for a maximum), or null.
+ *   sep_pair_bwd             d_est[b][i][t] = gw[b] (cT tgt[b][perm[i]][t] + cE est[b][i][t]) with cT x + cE y = d m / d y of the pair (i, perm[i]).
+ *                            gw (B) fp32 is the gradient arriving at EVERY per-source measure of item b (fold the 1 / n of a mean and the sign of
+ *                            a loss into it).  Reads two rows and writes one per estimate; every element of d_est is written.  A perm entry
+ *                            outside [0, n) is read as 0. */
+#define SEP_PAIR_SLAB 2048
+#define SEP_ASSIGN_MAX_N 64
+size_t sep_pair_gram_scratch_bytes(int B, int n, int T);
+int sep_pair_gram(const float* est, const float* tgt, double* dots, double* tt, double* xx, double* scratch, size_t scratch_bytes, int B, int n, int T,
+                  sep_stream_t stream);
+int sep_assign(const double* cost, int B, int n, int maximize, int64_t* perm, double* total, double* duals, sep_stream_t stream);
+int sep_pair_assign(const double* dots, const double* tt, const double* xx, int B, int n, int kind, int maximize, int use_mean, double eps, double tau,
+                    float* best_val, int64_t* perm, float* per_src, double* duals, sep_stream_t stream);
+int sep_pair_bwd(const float* est, const float* tgt, const double* dots, const double* tt, const double* xx, const int64_t* perm, const float* gw,
+                 float* d_est, int B, int n, int T, int kind, double eps, double tau, sep_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
