@@ -485,6 +485,15 @@ class ConvTasNet(nn.Module):
         from sepkernels.online import OnlineSeparator
         return OnlineSeparator(self, num_streams=num_streams, chunk_size=chunk_size, record=record, max_recordings=max_recordings)
 
+    def separate_long(self, mixture, window, hop=None, batch_windows=16):
+        """sepkernels.longform.separate_long(self, ...): a recording longer than the segments the model was trained on, separated in overlapping
+        windows of `window` samples at stride `hop` (default window // 2, window / 2 <= hop < window), `batch_windows` per forward, the windows'
+        outputs brought into one order by matching neighbours on the samples they share and cross-faded.  mixture (T,), (1, T) or
+        (batch_size, 1, T) -> (n_sources, T) or (batch_size, n_sources, T); for T <= window it is self(mixture).  Runs without a tape and leaves
+        train() / eval() to the caller.  Not the forward of the whole recording: gLN and the masks see one window at a time."""
+        from sepkernels.longform import separate_long
+        return separate_long(self, mixture, window, hop=hop, batch_windows=batch_windows)
+
     def _run_composed(self, mixture, want_latent):
         """The reference's own sequence (conv_tasnet.py:121-171) on this repository's modules, for configurations outside
         the fused family: pad -> encoder -> separator -> mask * w -> decoder (transposed convolution = overlap-add) -> crop.

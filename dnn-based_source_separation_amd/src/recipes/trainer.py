@@ -22,6 +22,7 @@ import torch
 from utils.checkpoint import load_checkpoint
 import torch.distributed as dist
 
+from sepkernels.longform import separate_long
 from sepkernels.train import FusedTrainStep
 
 from .audio_io import write_wav
@@ -191,7 +192,9 @@ class Tester:
     reference's tester (driver.py:297-309) through utils.bss.bss_eval_sources: SDR and SIR improvement -- the metric of the
     estimates minus the metric of the mixture repeated n_sources times -- and SAR of the estimates, per utterance and as
     `sdr_improvement`, `sir_improvement`, `sar` of the result.  (The reference additionally calls PESQ, which is not part
-    of this path: driver.py:277-370.)"""
+    of this path: driver.py:277-370.)  With `args.long_form_window` (samples; default unset) a mixture longer than that is
+    separated window by window at stride `args.long_form_hop` (default half the window) and stitched
+    (sepkernels.longform.separate_long) instead of in one forward; everything after the estimates is unchanged."""
 
     def __init__(self, model, loader, pit_criterion, args):
         self.model, self.loader, self.pit_criterion = model, loader, pit_criterion
@@ -201,6 +204,8 @@ class Tester:
             os.makedirs(self.out_dir, exist_ok=True)
         self.device = next(model.parameters()).device
         self.bss_eval = bool(getattr(args, "bss_eval", False))
+        self.long_form_window = getattr(args, "long_form_window", None)
+        self.long_form_hop = getattr(args, "long_form_hop", None)
         if getattr(args, "model_path", None):
             ck = load_checkpoint(args.model_path, getattr(args, "trust_pickle", None))
             model.load_state_dict(ck["state_dict"])
@@ -216,7 +221,10 @@ class Tester:
         print("ID, Loss, Loss improvement, SI-SDR improvement" + (", SDR improvement, SIR improvement, SAR" if self.bss_eval else ""), flush=True)
         with torch.no_grad():
             for idx, (mixture, sources, ids) in enumerate(DevicePrefetcher(self.loader, self.device)):
-                output = self.model(mixture)
+                if self.long_form_window and mixture.shape[-1] > self.long_form_window:
+                    output = separate_long(self.model, mixture, self.long_form_window, hop=self.long_form_hop)
+                else:
+                    output = self.model(mixture)
                 rep = mixture.expand(-1, self.n_sources, -1).contiguous()
                 loss_mix, _ = self.pit_criterion(rep, sources, batch_mean=False)
                 loss, perm = self.pit_criterion(output, sources, batch_mean=False)

@@ -251,6 +251,10 @@ SIGNATURES = {
     "sep_assign": [_vp] + [_I] * 3 + [_vp] * 3 + [_vp],
     "sep_pair_assign": [_vp] * 3 + [_I] * 5 + [_D, _D] + [_vp] * 4 + [_vp],
     "sep_pair_bwd": [_vp] * 8 + [_I] * 4 + [_D, _D] + [_vp],
+    # stitching the windows of a long recording (ABI 23, additive): pair costs on the overlaps, the chain of per-boundary matchings, the permuted cross-fade
+    "sep_stitch_cost": [_vp, _vp] + [_I] * 5 + [_vp],
+    "sep_stitch_chain": [_vp, _vp] + [_I] * 3 + [_vp],
+    "sep_stitch_ola": [_vp] * 3 + [_I] * 6 + [_vp],
 }
 _RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_last_kernel": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
              "sep_gln_tokens_ws_bytes": ctypes.c_size_t, "sep_online_state_row_bytes": ctypes.c_size_t, "sep_bss_scratch_bytes": ctypes.c_size_t,
@@ -957,6 +961,17 @@ class HipBackend:
     def pair_bwd(self, est, tgt, dots, tt, xx, perm, gw, d_est, B, n, T, kind, eps, tau):
         _check(load().sep_pair_bwd(_ptr(est, _f32), _ptr(tgt, _f32), _ptr(dots, _f64), _ptr(tt, _f64), _ptr(xx, _f64), _ptr(perm, torch.int64), _ptr(gw, _f32),
                                    _ptr(d_est, _f32), B, n, T, kind, eps, tau, _stream()), "sep_pair_bwd")
+
+    # ... stitching (sepkernels/longform.py): est (B, W, n, win) fp32; cost (B, W - 1, n, n) fp64; perm_local (B, W - 1, n), perm_abs (B, W, n) int64;
+    # out (B, n, T) fp32.  With W = 1 there is no boundary: cost / perm_local may be None
+    def stitch_cost(self, est, cost, B, W, n, win, hop):
+        _check(load().sep_stitch_cost(_ptr(est, _f32), _ptr(cost, _f64), B, W, n, win, hop, _stream()), "sep_stitch_cost")
+
+    def stitch_chain(self, perm_local, perm_abs, B, W, n):
+        _check(load().sep_stitch_chain(_ptr(perm_local, torch.int64), _ptr(perm_abs, torch.int64), B, W, n, _stream()), "sep_stitch_chain")
+
+    def stitch_ola(self, est, perm_abs, out, B, W, n, win, hop, T):
+        _check(load().sep_stitch_ola(_ptr(est, _f32), _ptr(perm_abs, torch.int64), _ptr(out, _f32), B, W, n, win, hop, T, _stream()), "sep_stitch_ola")
 
 
 _backend = HipBackend()

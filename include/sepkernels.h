@@ -849,6 +849,34 @@ int sep_pair_assign(const double* dots, const double* tt, const double* xx, int 
 int sep_pair_bwd(const float* est, const float* tgt, const double* dots, const double* tt, const double* xx, const int64_t* perm, const float* gw,
                  float* d_est, int B, int n, int T, int kind, double eps, double tau, sep_stream_t stream);
 
+/* ---- Stitching the windows of a long recording (continuous speech separation; ABI 23, additive; csrc/stitch.hip, sepkernels/longform.py) ----------
+ * A recording is separated window by window: est (B, W, n, win) fp32, contiguous, holds the n outputs of W windows of `win` samples at stride
+ * `hop` (window w covers samples [w hop, w hop + win) of the recording).  Neighbours share O = win - hop samples.  The outputs of a window come in
+ * an order of their own; the calls below find the order of every window relative to the first and join the windows into n tracks.
+ * 1 <= n <= SEP_ASSIGN_MAX_N, B >= 1, W >= 1, win / 2 <= hop < win (a sample lies in at most two windows), win <= 2^30.  Anything else is refused
+ * with a message before any launch.  All offsets are 64-bit.
+ *   sep_stitch_cost    cost (B, W - 1, n, n) fp64: cost[b][w][i][j] = sum_{t < O} (est[b][w][i][hop + t] - est[b][w + 1][j][t])^2, difference, square
+ *                      and sum in fp64: the layout sep_assign takes as B (W - 1) matrices (maximize = 0).  WRITTEN, not accumulated.  One
+ *                      workgroup per (boundary, 8 x 8 tile of pairs; 4 x 4 for n <= 4) walks the whole overlap with the tile in fp64 registers:
+ *                      no scratch, no second launch, no atomics -- per thread in ascending time, a wave butterfly, the four waves in order, so
+ *                      two runs give the same bits and identical rows cost exactly 0.  16-byte loads when win and hop are multiples of 4 and est
+ *                      is 16-byte aligned, sample by sample otherwise.  B (W - 1) < 2^31.  W = 1 launches nothing (cost may be null).
+ *   sep_stitch_chain   perm_local (B, W - 1, n) int64 as sep_assign writes it for those matrices (row i of window w is matched to row
+ *                      perm_local[b][w][i] of window w + 1) -> perm_abs (B, W, n) int64, the row of every window that continues track s:
+ *                      perm_abs[b][0][s] = s, perm_abs[b][w + 1][s] = perm_local[b][w][perm_abs[b][w][s]].  Sequential in w: one wavefront per
+ *                      recording, lane s, perm_local staged through LDS 64 windows at a time.  An entry of perm_local outside [0, n) is read as
+ *                      0 (sep_pair_bwd's convention): nothing is indexed out of range, every entry of perm_abs lies in [0, n).  W = 1 writes
+ *                      the identity (perm_local may be null).
+ *   sep_stitch_ola     out (B, n, T) fp32, 1 <= T <= (W - 1) hop + win, B <= 65535.  For sample t: w = min(t / hop, W - 1), k = t - w hop,
+ *                      c = est[b][w][perm_abs[b][w][s]][k].  If w >= 1 and k < O the sample lies in the overlap with the window before and
+ *                      out[b][s][t] = a + g (c - a) with a = est[b][w - 1][perm_abs[b][w - 1][s]][hop + k], g = (k + 0.5f) / O, all in fp32: a
+ *                      linear cross-fade whose weights add to one, so no normaliser.  Otherwise out[b][s][t] = c, a copy bit for bit.  Every
+ *                      element is written, each once, by the thread that owns it: no atomics.  An entry of perm_abs outside [0, n) is read as 0.
+ *                      16-byte loads and stores when win, hop and T are multiples of 4 and est, out are 16-byte aligned. */
+int sep_stitch_cost(const float* est, double* cost, int B, int W, int n, int win, int hop, sep_stream_t stream);
+int sep_stitch_chain(const int64_t* perm_local, int64_t* perm_abs, int B, int W, int n, sep_stream_t stream);
+int sep_stitch_ola(const float* est, const int64_t* perm_abs, float* out, int B, int W, int n, int win, int hop, int T, sep_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
