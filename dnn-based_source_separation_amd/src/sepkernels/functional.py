@@ -314,23 +314,31 @@ def _heads_widths(v, Wo, Ws):
 
 def heads_forward(v, n_frames, Wo, bo, Ws, bs, x_res, total, a_amax=None):
     """-> xo (None without the output head), total (created when None, else updated in place)"""
-    K = backend()
     B, _, ldt = v.shape
-    H, Bn, Sc = _heads_widths(v, Wo, Ws)
     f32 = dict(device=v.device, dtype=v.dtype)
     first = total is None
     if first:
-        total = torch.empty(B, Sc, ldt, **f32)
-    xo = torch.empty(B, Bn, ldt, **f32) if Wo is not None else None
+        total = torch.empty(B, Ws.shape[0], ldt, **f32)
+    xo = torch.empty(B, Wo.shape[0], ldt, **f32) if Wo is not None else None
+    heads_launch(v, n_frames, Wo, bo, Ws, bs, x_res, xo, total, int(not first), a_amax)
+    return xo, total
+
+
+def heads_launch(v, n_frames, Wo, bo, Ws, bs, x_res, xo, total, accumulate, a_amax=None):
+    """The launches of a layer's heads into memory the caller owns: xo (B, Bn, ldt) = Wo v + bo + x_res (not touched without the output head),
+    total (B, Sc, ldt) = Ws v + bs, added to what total holds when `accumulate`.  The one place that decides between the joint [Wo; Ws]
+    product and two products, for the training path (heads_forward) and the online chunk step (one (1, C, ldt) block over all streams) alike."""
+    K = backend()
+    B, _, ldt = v.shape
+    H, Bn, Sc = _heads_widths(v, Wo, Ws)
     joint = Wo is not None and bo is not None and bs is not None and Bn % 128 == 0 and _net._adjacent(Wo, Ws) and _net._adjacent(bo, bs)
     if joint:
         K.pw_gemm(B=B, M=Bn + Sc, K=H, T=n_frames, ldt=ldt, A=Wo.as_strided((Bn + Sc, H), (H, 1)), X=v, Y=xo, Y2=total, m_split=Bn,
-                  bias=bo.as_strided((Bn + Sc,), (1,)), accumulate=int(not first), epi_flags=_net.EPI_RESIDUAL, epi_res=x_res, a_amax=a_amax)
+                  bias=bo.as_strided((Bn + Sc,), (1,)), accumulate=accumulate, epi_flags=_net.EPI_RESIDUAL, epi_res=x_res, a_amax=a_amax)
     else:
         if Wo is not None:
             K.pw_gemm(B=B, M=Bn, K=H, T=n_frames, ldt=ldt, A=Wo, X=v, Y=xo, bias=bo, epi_flags=_net.EPI_RESIDUAL, epi_res=x_res, a_amax=a_amax)
-        K.pw_gemm(B=B, M=Sc, K=H, T=n_frames, ldt=ldt, A=Ws, X=v, Y=total, bias=bs, accumulate=int(not first), a_amax=a_amax)
-    return xo, total
+        K.pw_gemm(B=B, M=Sc, K=H, T=n_frames, ldt=ldt, A=Ws, X=v, Y=total, bias=bs, accumulate=accumulate, a_amax=a_amax)
 
 
 def heads_backward(v, Wo, Ws, a_amax, n_frames, d_out, d_total, dWo=None, dbo=None, dWs=None, dbs=None):

@@ -21,8 +21,9 @@ A chunk step is net.py-style orchestration: backend calls only, no autograd and 
 n frames are columns stream * n + frame of one (C, ldt) matrix ("stream-major"), so each 1x1 product of a layer is ONE sep_pw_gemm over all
 streams; the state that carries from chunk to chunk (encoder carry, frame counters, the cLN running sums, the depthwise histories, the
 overlap-add tail) lives in device memory and is read by the kernels of csrc/online.hip.  The first chunk of `chunk_size` samples is recorded
-(sepkernels.recording) and later chunks of that size replay it with one sep_run_sequence call; other sizes run the same launches eagerly on
-workspaces cached per size.  No gradients: training is out of scope.
+(sepkernels.recording) and later chunks of that size replay it with one sep_run_sequence call; other sizes run the same launches eagerly.
+Every call, whichever of the forms below it takes, goes through one path (OnlineSeparator._call: check, workspace, upload, record or replay,
+clone) on one workspace per chunk width.  No gradients: training is out of scope.
 
 Streams on their own clocks.  A separator is a set of `num_streams` SLOTS; sep(chunk, streams=...) advances only the slots it names and
 flush(streams) / reset(streams) end / restart only those, so the contract above holds PER STREAM whichever other streams took part in which
@@ -38,10 +39,12 @@ indices out of range, an empty selection and a chunk whose rows do not match the
 chunk length.  The pass of a subset call runs over the A selected streams only -- A n stream-major columns, T = A n in every product, A
 workgroups (or rows of workgroups) in the state kernels, the sep_online_*_sel entry points -- so idle slots cost their memory and nothing
 else.  The slot list lives in a device buffer of the workspace that is filled before every call like the chunk, so a step recorded for (A, n)
-replays for ANY selection of A slots.  One workspace per chunk length serves every A: its matrices are laid out with the leading dimension
-round_up(A n, 128) inside storage sized for all slots, and a recording per A holds a launch list only.  At most `max_recordings` (default 8)
+replays for ANY selection of A slots.  One workspace per chunk length serves every A and the all-streams call: a pass's matrices are laid out
+with the leading dimension round_up(A n, 128) inside storage sized for all slots, and a recording per A holds a launch list only.  At most `max_recordings` (default 8)
 of them are kept, the least recently used one is dropped first -- a recording owns no device memory of its own, so dropping one is safe at
-any time and the next call of that A records again.  streams=None is the all-streams call: it issues exactly the launches it always did.
+any time and the next call of that A records again.  streams=None is the all-streams call: it issues exactly the launches it always did, and
+its recording is kept apart from those -- not counted against `max_recordings`, never dropped for one of them.  When model.to() has replaced
+the flat parameter buffer the recordings were made under, all of them are dropped and made again.
 
 Ragged calls.  With `lengths` every stream of a call brings its own number of samples, so one pass carries whatever each stream has right now:
 
@@ -76,12 +79,14 @@ recorded step stays valid.  An imported slot behaves exactly as the exported one
 unchanged.  Whether the WEIGHTS are the same cannot be checked cheaply and is not checked.
 """
 import collections
+import itertools
+import types
 
 import torch
 
 import sepkernels
-from . import backend, EPI_RESIDUAL, EPI_SIGMOID, PRO_PRELU
-from . import net as _net
+from . import backend, EPI_SIGMOID, PRO_PRELU
+from . import functional as _fn
 
 
 def _round_up(a, b):
@@ -89,56 +94,38 @@ def _round_up(a, b):
 
 
 class _Workspace:
-    """the activations of one chunk size (n frames per stream): (C, ldt) stream-major matrices, columns [num_streams n, ldt) zero"""
-
-    def __init__(self, sep, n):
-        f = dict(device=sep.device, dtype=sep.dtype)
-        Bs, H, Bn, Sc, N = sep.num_streams, sep.H, sep.Bn, sep.Sc, sep.N
-        self.n = n
-        self.ldt = ldt = _round_up(Bs * n, 128)
-        self.chunk = torch.zeros(Bs, n * sep.S, **f)
-        self.w = torch.zeros(N, ldt, **f)
-        self.wn = torch.zeros(N, ldt, **f)
-        self.xa, self.xb = torch.zeros(Bn, ldt, **f), torch.zeros(Bn, ldt, **f)
-        self.ha, self.hb = torch.zeros(H, ldt, **f), torch.zeros(H, ldt, **f)
-        self.total = torch.zeros(Sc, ldt, **f)
-        self.m = torch.zeros(sep.n_src * N, ldt, **f)
-        self.out = torch.zeros(Bs, sep.n_src, n * sep.S, **f)
-        self.amax = torch.zeros(1, **f)
-        if sep.dense:                                          # separable=False: the normalised activation unfolded over the taps, rows c P + p
-            self.cols = torch.zeros(H * sep.P, ldt, **f)
-
-
-class _Views:
-    """what _step takes as a workspace: the matrices of one pass over `blocks` column blocks of n frames"""
-
-
-class _SubsetWorkspace:
-    """the activations of the subset calls of one chunk size: storage for all slots, handed out as (C, ldt_A) matrices with
-    ldt_A = round_up(A n, 128) for a call over A of them (every kernel of the pass that writes a matrix zeroes its columns [A n, ldt_A))"""
+    """the activations of every call of one chunk width (n frames per row): storage for all slots, handed out as the (C, ldt) stream-major
+    matrices of one pass.  Passes of different ldt share the storage, so a pass finds another's leftovers in its dead columns: every kernel
+    of a pass that writes a matrix zeroes its own columns [T, ldt), and a column of a product depends on that column alone"""
 
     def __init__(self, sep, n):
         f = dict(device=sep.device, dtype=sep.dtype)
         Bs = sep.num_streams
         self.n = n
-        self.ldt = ldt = _round_up(Bs * n, 128)
+        ldt = _round_up(Bs * n, 128)
         self.chunk = torch.zeros(Bs, n * sep.S, **f)
         self.out = torch.zeros(Bs, sep.n_src, n * sep.S, **f)
-        self.slots = torch.zeros(Bs, device=sep.device, dtype=torch.int32)
-        self.offs = torch.zeros(Bs + 1, device=sep.device, dtype=torch.int32)     # ragged calls: the column block of every stream
+        self.slots = torch.zeros(Bs, device=sep.device, dtype=torch.int32)        # calls on a selection: the slot of every row
+        self.offs = torch.zeros(Bs + 1, device=sep.device, dtype=torch.int32)     # ragged calls: the column block of every row
         self.amax = torch.zeros(1, **f)
         self.rows = dict(w=sep.N, wn=sep.N, xa=sep.Bn, xb=sep.Bn, ha=sep.H, hb=sep.H, total=sep.Sc, m=sep.n_src * sep.N)
-        if sep.dense:
+        if sep.dense:                                          # separable=False: the normalised activation unfolded over the taps, rows c P + p
             self.rows["cols"] = sep.H * sep.P
         self.store = {k: torch.zeros(C * ldt, **f) for k, C in self.rows.items()}
+        self.cache = {}                                        # (blocks, ldt) -> views: a stream of calls asks for the same few again and again
 
-    def views(self, A, ldt=None):
-        """ldt: of a ragged call (round_up of the frames it carries, 128); None: of a call whose A streams bring n frames each"""
-        v = _Views()
-        v.n, v.ldt = self.n, _round_up(A * self.n, 128) if ldt is None else ldt
-        for k, C in self.rows.items():
-            setattr(v, k, self.store[k][:C * v.ldt].view(C, v.ldt))
-        v.chunk, v.out, v.amax = self.chunk[:A], self.out[:A], self.amax
+    def views(self, blocks, ldt=None):
+        """-> what _step takes: the rows of chunk and out and the matrices of a pass over `blocks` column blocks.  ldt: of a ragged call
+        (round_up of the frames it carries, 128); None: of a call whose blocks bring n frames each, round_up(blocks n, 128)"""
+        ldt = _round_up(blocks * self.n, 128) if ldt is None else ldt
+        v = self.cache.get((blocks, ldt))
+        if v is None:
+            if len(self.cache) >= 256:                         # views own no memory: forgetting them costs the next calls their making, no more
+                self.cache.clear()
+            v = self.cache[blocks, ldt] = types.SimpleNamespace(ldt=ldt, chunk=self.chunk[:blocks], out=self.out[:blocks], amax=self.amax)
+            for k, C in self.rows.items():
+                setattr(v, k, self.store[k][:C * ldt].view(C, ldt))
+            v.block = {id(m): m.unsqueeze(0) for m in (getattr(v, k) for k in self.rows)}  # id(matrix) -> it as one (1, C, ldt) block of all streams
         return v
 
 
@@ -276,13 +263,12 @@ class OnlineSeparator:
         self.tail, self.tail_next = torch.zeros(Bs, self.n_src, keep, **f), torch.zeros(Bs, self.n_src, keep, **f)
         self.state_bytes = sum(t.numel() * t.element_size() for t in (self.frames, self.carry, self.carry_next, self.sums, self.rings, self.tail,
                                                                        self.tail_next))
-        self._ws = {}
-        self._seq = self._seq_n = self._seq_flat = None
         self.max_recordings = int(max_recordings)
-        self._sub_ws = {}                                      # chunk frames n (ragged calls: the row pitch in hops) -> _SubsetWorkspace
+        self._ws = {}                                          # chunk width in hops (ragged calls: the row pitch) -> _Workspace, for every call form
+        self._seq = None                                       # the all-streams step at chunk_size: apart from the bound and the eviction of the others
         self._sub_seqs = collections.OrderedDict()             # A (subset step) or (A, ldt) (ragged step) -> Sequence at chunk_size, least recently used first
-        self.replays = collections.Counter()                   # recording key -> how often it was replayed
-        self._sub_flat = None
+        self.replays = collections.Counter()                   # ragged recording key -> how often it was replayed
+        self._flat = None                                      # the model's flat parameter buffer the recordings were made under
         self._state_slots = None                               # export_state / import_state: the slot list on the device, filled before every call
 
     # ------------------------------------------------------------------ public
@@ -294,46 +280,17 @@ class OnlineSeparator:
         returns a list of (n_sources, k_j S)"""
         if isinstance(chunk, (list, tuple)):
             return self._call_list(chunk, streams, lengths)
-        if lengths is not None:
-            return self._call_ragged(chunk, self._select(streams) if streams is not None else list(range(self.num_streams)), lengths)
-        if streams is not None:
-            return self._call_subset(chunk, self._select(streams))
-        n = self._check_chunk(chunk)
-        with torch.no_grad():
-            ws = self._ws.get(n)
-            if ws is None:
-                ws = self._ws[n] = _Workspace(self, n)
-            ws.chunk.copy_(chunk.reshape(self.num_streams, n * self.S))
-            target = self.chunk_size if self.chunk_size is not None else n * self.S
-            if self.chunk_size is None:
-                self.chunk_size = target
-            if self.record and n * self.S == target:
-                flat = self.model.flat_parameters()
-                if self._seq is not None and self._seq_flat is not flat:       # model.to() since the recording: its pointers are stale
-                    self._seq = None
-                if self._seq is None:
-                    seq = sepkernels.Sequence()
-                    with sepkernels.recording(seq):
-                        self._step(ws, n)
-                    self._seq, self._seq_n, self._seq_flat = seq, n, flat
-                else:
-                    self._seq.run()
-            else:
-                self._step(ws, n)
-            return ws.out.clone()
+        if streams is None and lengths is not None:
+            streams = range(self.num_streams)
+        return self._call(chunk, self._select(streams) if streams is not None else None, lengths)
 
     def flush(self, streams=None):
         """the last L - S samples of every stream (num_streams, n_sources, L - S); then every stream is reset.  With `streams`: of the selected
         streams in the order given, (A, n_sources, L - S), and only they are reset"""
-        if streams is not None:
-            idx = self._select(streams)
-            with torch.no_grad():
-                out = self.tail.index_select(0, torch.tensor(idx, dtype=torch.int64).to(self.device))
-            self.reset(idx)
-            return out
+        idx = self._select(streams) if streams is not None else None
         with torch.no_grad():
-            out = self.tail.clone()
-        self.reset()
+            out = self.tail.clone() if idx is None else self.tail.index_select(0, torch.tensor(idx, dtype=torch.int64).to(self.device))
+        self.reset(idx)
         return out
 
     def reset(self, streams=None):
@@ -434,37 +391,6 @@ class OnlineSeparator:
             raise ValueError("duplicate stream indices in the selection: every selected stream takes one row of the chunk")
         return idx
 
-    def _call_subset(self, chunk, idx):
-        A = len(idx)
-        n = self._check_chunk(chunk, A)
-        with torch.no_grad():
-            ws = self._sub_ws.get(n)
-            if ws is None:
-                ws = self._sub_ws[n] = _SubsetWorkspace(self, n)
-            ws.chunk[:A].copy_(chunk.reshape(A, n * self.S))
-            ws.slots[:A].copy_(torch.tensor(idx, dtype=torch.int32))
-            if self.chunk_size is None:
-                self.chunk_size = n * self.S
-            if self.record and n * self.S == self.chunk_size:
-                flat = self.model.flat_parameters()
-                if self._sub_flat is not flat:                                  # model.to() since the recordings: their pointers are stale
-                    self._sub_seqs.clear()
-                    self._sub_flat = flat
-                seq = self._sub_seqs.get(A)
-                if seq is None:
-                    seq = sepkernels.Sequence()
-                    with sepkernels.recording(seq):
-                        self._step(ws.views(A), n, A, ws.slots)
-                    self._sub_seqs[A] = seq
-                    while len(self._sub_seqs) > self.max_recordings:           # a recording is a launch list: nothing on the device goes with it
-                        self._sub_seqs.popitem(last=False)
-                else:
-                    self._sub_seqs.move_to_end(A)
-                    seq.run()
-            else:
-                self._step(ws.views(A), n, A, ws.slots)
-            return ws.out[:A].clone()
-
     # ------------------------------------------------------------------ a call in which every stream brings its own length
     def _frames_of(self, lengths, A, W):
         """-> frames per row, checked"""
@@ -484,45 +410,55 @@ class OnlineSeparator:
                 raise ValueError("a length must be a positive multiple of the stride {} and at most the chunk's {} samples (got {})".format(self.S, W, v))
         return [v // self.S for v in lengths]
 
-    def _call_ragged(self, chunk, idx, lengths):
-        A = len(idx)
-        cap = self._check_chunk(chunk, A)
-        W = cap * self.S
-        counts = self._frames_of(lengths, A, W)
-        offs = [0]
-        for k in counts:
-            offs.append(offs[-1] + k)
-        ldt = _round_up(offs[-1], 128)
+    def _call(self, chunk, idx, lengths):
+        """every call: on the slots `idx` names, row j slot idx[j] (None: all of them, through the plain entry points); row j brings lengths[j]
+        samples (None: the whole chunk; else the ragged entry points)"""
+        A = self.num_streams if idx is None else len(idx)
+        n = self._check_chunk(chunk, None if idx is None else A)
+        W = n * self.S
+        offs = ldt = None
+        if lengths is not None:
+            offs = list(itertools.accumulate(self._frames_of(lengths, A, W), initial=0))
+            ldt = _round_up(offs[-1], 128)
         with torch.no_grad():
-            ws = self._sub_ws.get(cap)                                          # shared with the uniform subset calls of this width
+            ws = self._ws.get(n)
             if ws is None:
-                ws = self._sub_ws[cap] = _SubsetWorkspace(self, cap)
-            ws.chunk[:A].copy_(chunk.reshape(A, W))
-            ws.slots[:A].copy_(torch.tensor(idx, dtype=torch.int32))
-            ws.offs[:A + 1].copy_(torch.tensor(offs, dtype=torch.int32))
+                ws = self._ws[n] = _Workspace(self, n)
+            v = ws.views(A, ldt)
+            v.chunk.copy_(chunk.reshape(A, W))
+            if idx is not None:
+                ws.slots[:A].copy_(torch.tensor(idx, dtype=torch.int32))
+            if offs is not None:
+                ws.offs[:A + 1].copy_(torch.tensor(offs, dtype=torch.int32))
             if self.chunk_size is None:
                 self.chunk_size = W
+            step = (v, n, A, ws.slots if idx is not None else None, ws.offs if offs is not None else None)
             if self.record and W == self.chunk_size:
                 flat = self.model.flat_parameters()
-                if self._sub_flat is not flat:                                  # model.to() since the recordings: their pointers are stale
+                if self._flat is not flat:                                      # model.to() since the recordings: their pointers are stale
+                    self._seq, self._flat = None, flat
                     self._sub_seqs.clear()
-                    self._sub_flat = flat
-                key = (A, ldt)
-                seq = self._sub_seqs.get(key)
+                key = None if idx is None else A if offs is None else (A, ldt)
+                seq = self._seq if key is None else self._sub_seqs.get(key)
                 if seq is None:
                     seq = sepkernels.Sequence()
                     with sepkernels.recording(seq):
-                        self._step(ws.views(A, ldt), cap, A, ws.slots, ws.offs)
-                    self._sub_seqs[key] = seq
-                    while len(self._sub_seqs) > self.max_recordings:
-                        self._sub_seqs.popitem(last=False)
+                        self._step(*step)
+                    if key is None:
+                        self._seq = seq
+                    else:
+                        self._sub_seqs[key] = seq
+                        while len(self._sub_seqs) > self.max_recordings:       # a recording is a launch list: nothing on the device goes with it
+                            self._sub_seqs.popitem(last=False)
                 else:
-                    self._sub_seqs.move_to_end(key)
+                    if key is not None:
+                        self._sub_seqs.move_to_end(key)
                     seq.run()
-                    self.replays[key] += 1
+                    if offs is not None:
+                        self.replays[key] += 1
             else:
-                self._step(ws.views(A, ldt), cap, A, ws.slots, ws.offs)
-            return ws.out[:A].clone()
+                self._step(*step)
+            return v.out.clone()
 
     def _call_list(self, pieces, streams, lengths):
         if lengths is not None:
@@ -541,15 +477,15 @@ class OnlineSeparator:
         chunk = torch.zeros(len(rows), 1, max(sizes), device=self.device, dtype=self.dtype)
         for j, r in enumerate(rows):
             chunk[j, 0, :sizes[j]] = r
-        y = self._call_ragged(chunk, idx, sizes)
+        y = self._call(chunk, idx, sizes)
         return [y[j, :, :sizes[j]] for j in range(len(rows))]
 
     # ------------------------------------------------------------------ the chunk step
     def _check_chunk(self, chunk, rows=None):
-        if rows is not None and (not torch.is_tensor(chunk) or chunk.dim() != 3 or chunk.shape[0] != rows or chunk.shape[1] != 1):
-            raise ValueError("a chunk for {} selected streams is ({}, 1, k*{}) (got {})".format(rows, rows, self.S, tuple(getattr(chunk, "shape", ()))))
-        if rows is None and (not torch.is_tensor(chunk) or chunk.dim() != 3 or chunk.shape[0] != self.num_streams or chunk.shape[1] != 1):
-            raise ValueError("a chunk is (num_streams={}, 1, k*{}) (got {})".format(self.num_streams, self.S, tuple(getattr(chunk, "shape", ()))))
+        want = self.num_streams if rows is None else rows
+        if not torch.is_tensor(chunk) or chunk.dim() != 3 or chunk.shape[0] != want or chunk.shape[1] != 1:
+            what = "a chunk is (num_streams={}".format(want) if rows is None else "a chunk for {} selected streams is ({}".format(want, want)
+            raise ValueError("{}, 1, k*{}) (got {})".format(what, self.S, tuple(getattr(chunk, "shape", ()))))
         T = chunk.shape[-1]
         if T == 0 or T % self.S:
             raise ValueError("a chunk's length must be a positive multiple of the stride {} (got {})".format(self.S, T))
@@ -559,27 +495,19 @@ class OnlineSeparator:
             raise ValueError("the chunk must be on {} in {} like the separator's state (got {} {})".format(self.device, self.dtype, chunk.device, chunk.dtype))
         return T // self.S
 
-    def _step(self, ws, n, blocks=None, slots=None, offs=None):
-        """one chunk of n frames of every stream: ~5 launches per TCN layer plus encoder, norm, bottleneck, mask, decoder and advance
-        (separable=False: conv1, cLN, online unfold, heads -- 4 or 5).
-        With `slots` (device int32): of the `blocks` streams it names, through the sep_online_*_sel entry points.  With `offs` too (device
-        int32, blocks + 1 entries): stream j brings offs[j + 1] - offs[j] <= n frames, through the sep_online_*_rag entry points, and the
-        products run over all ws.ldt columns"""
+    def _step(self, ws, n, blocks, slots=None, offs=None):
+        """one chunk of n frames of `blocks` streams on the matrices `ws` (_Workspace.views): ~5 launches per TCN layer plus encoder, norm,
+        bottleneck, mask, decoder and advance (separable=False: conv1, cLN, online unfold, heads -- 4 or 5).  The pointers pick the form, as in
+        csrc/online.hip.  Without `slots`: block j is slot j, the plain entry points.  With `slots` (device int32): block j is slot slots[j],
+        the sep_online_*_sel entry points.  With `offs` too (device int32, blocks + 1 entries): block j brings offs[j + 1] - offs[j] <= n
+        frames, the sep_online_*_rag entry points, and the products run over all ws.ldt columns"""
         K = backend()
         model, sep = self.model, self.model.separator
-        Bs, L, S, N, H, Bn, Sc, n_src = self.num_streams, self.L, self.S, self.N, self.H, self.Bn, self.Sc, self.n_src
-        taps = "online_unfold_fwd" if self.dense else "online_depthwise_fwd"      # the kernel that keeps a layer's history
-        if slots is None:
-            encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd, K.online_cln_fwd, getattr(K, taps), K.online_decoder_fwd,
-                                                                  K.online_advance, ())
-        elif offs is None:
-            encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd_sel, K.online_cln_fwd_sel, getattr(K, taps + "_sel"),
-                                                                  K.online_decoder_fwd_sel, K.online_advance_sel, (slots,))
-            Bs = blocks
-        else:
-            encoder, cln_fwd, depthwise, decoder, advance, sel = (K.online_encoder_fwd_rag, K.online_cln_fwd_rag, getattr(K, taps + "_rag"),
-                                                                  K.online_decoder_fwd_rag, K.online_advance_rag, (slots, offs))
-            Bs = blocks
+        Bs, L, S, N, H, Bn, Sc, n_src = blocks, self.L, self.S, self.N, self.H, self.Bn, self.Sc, self.n_src
+        taps = "unfold_fwd" if self.dense else "depthwise_fwd"                    # the kernel that keeps a layer's history
+        form, sel = ("", ()) if slots is None else ("_sel", (slots,)) if offs is None else ("_rag", (slots, offs))
+        encoder, cln_fwd, depthwise, decoder, advance = (getattr(K, "online_" + k + form)
+                                                         for k in ("encoder_fwd", "cln_fwd", taps, "decoder_fwd", "advance"))
         T, ldt = (Bs * n if offs is None else ws.ldt), ws.ldt
         keep = self.delay
         sums, sstride = self.sums.view(-1), 2 * self.n_norms
@@ -592,6 +520,12 @@ class OnlineSeparator:
         def cln(x, y, norm, alpha, i):
             cln_fwd(x, alpha, norm.gamma.reshape(-1), norm.beta.reshape(-1), y, sums[2 * i:], sstride, self.frames, Bs, x.shape[0], n, ldt,
                     norm.eps, *sel)
+
+        def heads(v, out, skip, x_res, x_out, li):
+            # x_out = Wo v + bo + x_res, total (+)= Ws v + bs as the training path issues them: the (C, ldt) matrices as one block of all streams
+            Wo, bo = (out.weight, out.bias) if out is not None else (None, None)
+            b = ws.block
+            _fn.heads_launch(b[id(v)], T, Wo, bo, skip.weight, skip.bias, b[id(x_res)], b[id(x_out)], b[id(ws.total)], int(li > 0), amax)
 
         encoder(ws.chunk, model.encoder.conv1d.weight, self.carry if keep else None, self.carry_next if keep else None, ws.w, Bs, N, L, S,
                 n, ldt, model.enc_nonlinear == "relu", *sel)
@@ -607,7 +541,7 @@ class OnlineSeparator:
                 cln(ws.ha, ws.hb, layer.norm1d, layer.nonlinear1d.weight, 1 + li)
                 depthwise(ws.hb, rings[self.ring_offsets[li]:], self.ring_len, ws.cols, Bs, H, n, ldt, P, d, *sel)
                 out = layer.output_conv1d if layer.dual_head else None
-                self._heads(K, ws.cols, out, layer.skip_conv1d, x, x_next, ws.total, li == 0, T, ldt, amax)
+                heads(ws.cols, out, layer.skip_conv1d, x, x_next, li)
                 if out is not None:
                     x, x_next = x_next, x
                 continue
@@ -617,7 +551,7 @@ class OnlineSeparator:
                       Bs, H, n, ldt, P, d, *sel)
             cln(ws.ha, ws.hb, dw.norm1d, dw.nonlinear1d.weight, 2 + 2 * li)
             out = dw.output_pointwise_conv1d if dw.dual_head else None
-            self._heads(K, ws.hb, out, dw.skip_pointwise_conv1d, x, x_next, ws.total, li == 0, T, ldt, amax)
+            heads(ws.hb, out, dw.skip_pointwise_conv1d, x, x_next, li)
             if out is not None:
                 x, x_next = x_next, x
         M = n_src * N
@@ -629,23 +563,6 @@ class OnlineSeparator:
                 Bs, n_src, N, L, S, n, ldt, *sel)
         advance(self.frames, self.carry if keep else None, self.carry_next if keep else None, keep, self.tail if keep else None,
                 self.tail_next if keep else None, n_src * keep, Bs, n, *sel)
-
-    @staticmethod
-    def _heads(K, v, out, skip, x_res, x_out, total, first, T, ldt, amax):
-        """the two 1x1 heads of a layer as sepkernels.functional.PaddedHeadsFn.forward issues them: x_out = Wo v + bo + x_res, total (+)= Ws v + bs"""
-        H = v.shape[0]
-        Ws, bs = skip.weight, skip.bias
-        Sc = Ws.shape[0]
-        Wo, bo = (out.weight, out.bias) if out is not None else (None, None)
-        Bn = Wo.shape[0] if Wo is not None else 0
-        joint = Wo is not None and bo is not None and bs is not None and Bn % 128 == 0 and _net._adjacent(Wo, Ws) and _net._adjacent(bo, bs)
-        if joint:
-            K.pw_gemm(B=1, M=Bn + Sc, K=H, T=T, ldt=ldt, A=Wo.as_strided((Bn + Sc, H), (H, 1)), X=v, Y=x_out, Y2=total, m_split=Bn,
-                      bias=bo.as_strided((Bn + Sc,), (1,)), accumulate=int(not first), epi_flags=EPI_RESIDUAL, epi_res=x_res, a_amax=amax)
-            return
-        if Wo is not None:
-            K.pw_gemm(B=1, M=Bn, K=H, T=T, ldt=ldt, A=Wo, X=v, Y=x_out, bias=bo, epi_flags=EPI_RESIDUAL, epi_res=x_res, a_amax=amax)
-        K.pw_gemm(B=1, M=Sc, K=H, T=T, ldt=ldt, A=Ws, X=v, Y=total, bias=bs, accumulate=int(not first), a_amax=amax)
 
     def launches_per_chunk(self):
         """launches of one recorded all-streams chunk step (None before the first recorded one; a subset step issues as many)"""

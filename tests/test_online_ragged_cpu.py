@@ -252,11 +252,11 @@ def test_recorded_ragged_steps_equal_eager_launches_bitwise(on_host):
             tails = sep.flush(list(range(5)))
             runs.append([torch.cat(outs[s] + [tails[s]], -1) for s in range(5)])
             if record:
-                assert len(sep._sub_seqs) == 2 and set(sep._sub_seqs) <= keys and len(sep._sub_ws) == 1 and sum(sep.replays.values()) >= 1
+                assert len(sep._sub_seqs) == 2 and set(sep._sub_seqs) <= keys and len(sep._ws) == 1 and sum(sep.replays.values()) >= 1
                 ragged = {len(q) for q in sep._sub_seqs.values()}
                 sep(torch.zeros(2, 1, cap * S), streams=[0, 1])             # a subset step of the same model, recorded
                 assert ragged == {len(sep._sub_seqs[2])} and len(sep._sub_seqs[2]) > 10
-                assert len(sep._sub_ws) == 1                                # ragged and uniform subset calls of one width share a workspace
+                assert len(sep._ws) == 1                                # ragged and uniform subset calls of one width share a workspace
         with torch.no_grad():
             refs = [model(F.pad(x[s:s + 1, :, :done[s] * S], (L - S, 0)))[0] for s in range(5)]
     finally:

@@ -10,7 +10,8 @@
 (c) the refusals.
 (d), (e) the kernel SOURCE on the host (tools/hostsim.py): the kernel cases of tests/test_online_streams_gpu.py, and a tiny model streamed with
     subset calls, recorded against eager, with more distinct selection sizes than recordings are kept.
-(f) streams=None and streams=list(range(num_streams)) agree."""
+(f) streams=None and streams=list(range(num_streams)) agree.
+(g) on the kernel sources: all-streams, subset and ragged calls interleaved at one width share one workspace, recorded against eager."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -221,7 +222,7 @@ def test_recorded_subset_steps_equal_eager_launches_bitwise(on_host):
                     done[s] += 1
                 assert len(sep._sub_seqs) <= 2
             if record:
-                assert len(sep._sub_seqs) == 2 and len(sep._sub_ws) == 1 and all(len(q) > 10 for q in sep._sub_seqs.values())
+                assert len(sep._sub_seqs) == 2 and len(sep._ws) == 1 and all(len(q) > 10 for q in sep._sub_seqs.values())
                 assert sep.launches_per_chunk() is None                     # no all-streams step was recorded
             tails = sep.flush(list(range(5)))
             runs.append([torch.cat(outs[s] + [tails[s]], -1) for s in range(5)])
@@ -232,3 +233,15 @@ def test_recorded_subset_steps_equal_eager_launches_bitwise(on_host):
     for s in range(5):
         assert torch.equal(runs[0][s], runs[1][s]), "slot {}: recorded differs from eager".format(s)
         assert OC._rel(runs[0][s], refs[s]) <= 1e-5, (s, OC._rel(runs[0][s], refs[s]))
+
+
+@needs_clang
+@pytest.mark.parametrize("unit", [1, 9])
+def test_all_streams_recording_replays_after_subset_and_ragged_passes_on_its_workspace(on_host, unit):
+    """the three call forms of the tiny model interleaved on one workspace (test_online_streams_gpu.check_mixed_forms_share_a_workspace) on the
+    kernel sources, to 1e-5 of every slot's maximum, the bar of the test above"""
+    old = sepkernels._set_backend_for_tests(OC._Named(on_host))
+    try:
+        SG.check_mixed_forms_share_a_workspace(OC._tiny(), 8, 4, 1e-5, unit)
+    finally:
+        sepkernels._set_backend_for_tests(old)

@@ -6,8 +6,9 @@ fp64 restatements of tests/test_online_gpu.py (bars as there: 2e-5 for outputs, 
 first chunk the unselected slots hold sentinels -- finite values in the state, NaN in carry_next / tail_next -- and afterwards every unselected
 entry is bitwise its sentinel.  tests/test_online_streams_cpu.py runs the same functions on the host simulation of the kernel sources (they go
 through test_online_gpu's HIP, to_device and device_sync, which it swaps).  The model tests drive the reference's fixture through a schedule in
-which every stream starts, pauses, ends and restarts on its own (run_schedule), and a paper-size model with a different half of 64 slots in
-every call."""
+which every stream starts, pauses, ends and restarts on its own (run_schedule), a paper-size model with a different half of 64 slots in
+every call, and all-streams, subset and ragged calls interleaved on the one workspace of their width (check_mixed_forms_share_a_workspace, also
+run by the CPU module on the kernel sources)."""
 import os
 
 import numpy as np
@@ -289,6 +290,64 @@ def test_fixture_on_independent_clocks_matches_the_reference_on_the_device(name,
             assert row == row_e and torch.equal(est, est_e), "recorded subset steps differ from eager launches"
     finally:
         sepkernels.set_gemm_arith(prev)
+
+
+# ------------------------------------------------------------------------------------------------------ the three call forms on one workspace
+# (slots, hops per slot) at the recorded width of 3 hops: slots None is the all-streams call, hops None a uniform call, an integer an all-streams
+# call at that other width.  The all-streams recording is replayed after subset and ragged passes have run over the storage it points into; the
+# subset and ragged calls change size, members and order; their recordings of A = 3 and of two rows with ldt 128 are replayed once each, then A = 2
+# and three ragged rows come in and push both out of the two that are kept.
+MIXED = [(None, None), ([3, 0, 4], None), (None, None), ([1, 4], [2, 3]), (None, None), ([4, 1, 0], None), ([0, 3], [3, 1]), ([2, 1], None),
+         (None, None), ([4, 0, 2], [1, 3, 2]), (None, 2), ([1, 2], None), (None, None)]
+
+
+def check_mixed_forms_share_a_workspace(model, L, S, tol, unit=1):
+    """5 slots, chunk_size 3 hops, max_recordings 2, the calls of MIXED (the eleventh runs eagerly), then every slot flushed.  A recording separator
+    and an eager one agree to the last bit for every slot; every slot's output is the offline forward on what it received within tol of its
+    maximum; the recorded width has one workspace; the all-streams recording is one object from its first call on, and at most two of the
+    others are kept at any time.  With unit = 1 every pass has ldt 128 and the passes differ in which columns they use; `unit` multiplies every
+    hop count, and at 9 the all-streams pass has ldt 256 and the subset and ragged passes 128 inside the same storage"""
+    flat = model.flat_parameters()
+    x = 0.1 * torch.randn(5, 1, 30 * unit * S, generator=torch.Generator().manual_seed(23)).to(device=flat.device, dtype=flat.dtype)
+    runs = []
+    for record in (True, False):
+        sep = model.online_separator(num_streams=5, chunk_size=3 * unit * S, record=record, max_recordings=2)
+        assert sep.record == record
+        pos, outs, first = [0] * 5, [[] for _ in range(5)], None
+        for slots, hops in MIXED:
+            idx = list(range(5)) if slots is None else slots
+            ragged = isinstance(hops, list)
+            n = unit * (hops if isinstance(hops, int) else 3)
+            counts = [unit * h for h in hops] if ragged else [n] * len(idx)
+            chunk = torch.zeros(len(idx), 1, n * S, device=x.device, dtype=x.dtype)
+            for j, (s, h) in enumerate(zip(idx, counts)):
+                chunk[j, 0, :h * S] = x[s, 0, pos[s] * S:(pos[s] + h) * S]
+            y = sep(chunk, streams=slots, lengths=[h * S for h in counts] if ragged else None)
+            assert y.shape == (len(idx), sep.n_src, n * S)
+            for j, (s, h) in enumerate(zip(idx, counts)):
+                assert not y[j, :, h * S:].any()
+                outs[s].append(y[j, :, :h * S])
+                pos[s] += h
+            first = sep._seq if first is None else first
+            assert sep._seq is first and len(sep._sub_seqs) <= 2 and 3 * unit in sep._ws and set(sep._ws) <= {3 * unit, 2 * unit}
+        if record:
+            assert first is not None and sep.launches_per_chunk() == len(first) and list(sep._sub_seqs) == [(3, 128), 2] and sum(sep.replays.values()) == 1
+        else:
+            assert first is None and not sep._sub_seqs
+        tails = sep.flush()
+        runs.append([torch.cat(outs[s] + [tails[s]], -1) for s in range(5)])
+    for s in range(5):
+        assert torch.equal(runs[0][s], runs[1][s]), "slot {}: recorded differs from eager".format(s)
+        with torch.no_grad():
+            ref = model(torch.nn.functional.pad(x[s:s + 1, :, :pos[s] * S], (L - S, 0)))[0]
+        close(runs[0][s], ref.cpu(), tol, "slot {} after {} hops".format(s, pos[s]))
+
+
+@pytest.mark.parametrize("unit", [1, 9])
+def test_all_streams_recording_replays_after_subset_and_ragged_passes_on_its_workspace(unit):
+    """causal16_p5 in the default arithmetic, to the 1e-3 bar of test_fixture_on_independent_clocks_matches_the_reference_on_the_device"""
+    model, cfg = OG._fixture_model("causal16_p5")
+    check_mixed_forms_share_a_workspace(model, cfg["kernel_size"], cfg["stride"], 1e-3, unit)
 
 
 def test_paper_size_model_with_a_different_half_of_64_slots_in_every_call():
