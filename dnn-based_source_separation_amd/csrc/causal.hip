@@ -263,11 +263,11 @@ extern "C" int sep_depthwise_cln_fwd(const float* x, const float* alpha, const f
     hipStream_t stream = (hipStream_t)stream_;
     const size_t bytes = (size_t)ldt * sizeof(float);
     const dim3 grid((unsigned)((long)B * C)), block(256);
-#define SEP_CDF(KW, ST) hipLaunchKernelGGL((cd_depthwise_fwd_kernel<KW, ST>), grid, block, ST ? bytes : (size_t)0, stream, x, alpha, gamma, beta, mean, rstd, w, bias, y, C, T, ldt, Kw, pad, dil)
+#define SEP_CDF(KW, ST) sep_set_kernel("cd_depthwise_fwd<" #KW "," #ST ">"); hipLaunchKernelGGL((cd_depthwise_fwd_kernel<KW, ST>), grid, block, ST ? bytes : (size_t)0, stream, x, alpha, gamma, beta, mean, rstd, w, bias, y, C, T, ldt, Kw, pad, dil)
     if (bytes <= CD_LDS_ROW_BYTES) {
-        if (Kw == 3) SEP_CDF(3, true); else SEP_CDF(0, true);
+        if (Kw == 3) { SEP_CDF(3, true); } else { SEP_CDF(0, true); }
     } else {
-        if (Kw == 3) SEP_CDF(3, false); else SEP_CDF(0, false);
+        if (Kw == 3) { SEP_CDF(3, false); } else { SEP_CDF(0, false); }
     }
 #undef SEP_CDF
     SEP_CHECK_LAUNCH("sep_depthwise_cln_fwd");
@@ -282,11 +282,11 @@ extern "C" int sep_depthwise_cln_bwd_weight(const float* dy, const float* x, con
     hipStream_t stream = (hipStream_t)stream_;
     const size_t bytes = (size_t)ldt * sizeof(float);
     const dim3 grid((unsigned)((long)B * C)), block(256);
-#define SEP_CDW(KW, ST) hipLaunchKernelGGL((cd_depthwise_wgrad_kernel<KW, ST>), grid, block, ST ? bytes : (size_t)0, stream, dy, x, alpha, gamma, beta, mean, rstd, partial, C, T, ldt, Kw, pad, dil)
+#define SEP_CDW(KW, ST) sep_set_kernel("cd_depthwise_wgrad<" #KW "," #ST ">"); hipLaunchKernelGGL((cd_depthwise_wgrad_kernel<KW, ST>), grid, block, ST ? bytes : (size_t)0, stream, dy, x, alpha, gamma, beta, mean, rstd, partial, C, T, ldt, Kw, pad, dil)
     if (bytes <= CD_LDS_ROW_BYTES) {
-        if (Kw == 3) SEP_CDW(3, true); else SEP_CDW(0, true);
+        if (Kw == 3) { SEP_CDW(3, true); } else { SEP_CDW(0, true); }
     } else {
-        if (Kw == 3) SEP_CDW(3, false); else SEP_CDW(0, false);
+        if (Kw == 3) { SEP_CDW(3, false); } else { SEP_CDW(0, false); }
     }
 #undef SEP_CDW
     SEP_CHECK_LAUNCH("sep_depthwise_cln_bwd_weight");

@@ -593,12 +593,13 @@ extern "C" int sep_cln_fwd(const float* x, const float* gamma, const float* beta
         SEP_REQUIRE((long)B * nt <= 0x7fffffffL / 4, "sep_cln_fwd: too many tiles");
         const ChainWs cw = chain_ws(ws, B, C, nt);
         SEP_REQUIRE(hipMemsetAsync(ws, 0, cw.clear_bytes, stream) == hipSuccess, "sep_cln: clearing the chain records failed");
-#define SEP_CLF(RR) hipLaunchKernelGGL((cln_chain_fwd_kernel<RR, true>), dim3(B * nt), dim3(512), 0, stream, x, gamma, beta, alpha, y, mean, rstd, cw.ticket, cw.agg, cw.incl, B, C, T, ldt, nt, eps)
-        if (C <= 64) SEP_CLF(1); else if (C <= 128) SEP_CLF(2); else if (C <= 256) SEP_CLF(4); else SEP_CLF(8);
+#define SEP_CLF(RR) sep_set_kernel("cln_chain_fwd<" #RR ",true>"); hipLaunchKernelGGL((cln_chain_fwd_kernel<RR, true>), dim3(B * nt), dim3(512), 0, stream, x, gamma, beta, alpha, y, mean, rstd, cw.ticket, cw.agg, cw.incl, B, C, T, ldt, nt, eps)
+        if (C <= 64) { SEP_CLF(1); } else if (C <= 128) { SEP_CLF(2); } else if (C <= 256) { SEP_CLF(4); } else { SEP_CLF(8); }
 #undef SEP_CLF
         SEP_CHECK_LAUNCH("sep_cln_fwd");
         return 0;
     }
+    sep_set_kernel("cln_three_fwd");
     hipLaunchKernelGGL((cln_colsums_kernel<false>), dim3(ceil_div(T, CLN_TCOLS), B), dim3(256), 0, stream, x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, alpha, ws, C, T, ldt);
     hipLaunchKernelGGL(cln_scan_fwd_kernel, dim3(B), dim3(1024), 0, stream, (const double*)ws, mean, rstd, C, T, ldt, eps);
     hipLaunchKernelGGL(cln_apply_fwd_kernel, dim3(ceil_div(C, 4), B), dim3(256), 0, stream, x, (const float*)mean, (const float*)rstd, gamma, beta, alpha, y, C, T, ldt);
@@ -618,12 +619,13 @@ extern "C" int sep_cln_stats(const float* x, float* mean, float* rstd, double* w
         SEP_REQUIRE((long)B * nt <= 0x7fffffffL / 4, "sep_cln_stats: too many tiles");
         const ChainWs cw = chain_ws(ws, B, C, nt);
         SEP_REQUIRE(hipMemsetAsync(ws, 0, cw.clear_bytes, stream) == hipSuccess, "sep_cln: clearing the chain records failed");
-#define SEP_CLS(RR) hipLaunchKernelGGL((cln_chain_fwd_kernel<RR, false>), dim3(B * nt), dim3(512), 0, stream, x, (const float*)nullptr, (const float*)nullptr, alpha, (float*)nullptr, mean, rstd, cw.ticket, cw.agg, cw.incl, B, C, T, ldt, nt, eps)
-        if (C <= 64) SEP_CLS(1); else if (C <= 128) SEP_CLS(2); else if (C <= 256) SEP_CLS(4); else SEP_CLS(8);
+#define SEP_CLS(RR) sep_set_kernel("cln_chain_fwd<" #RR ",false>"); hipLaunchKernelGGL((cln_chain_fwd_kernel<RR, false>), dim3(B * nt), dim3(512), 0, stream, x, (const float*)nullptr, (const float*)nullptr, alpha, (float*)nullptr, mean, rstd, cw.ticket, cw.agg, cw.incl, B, C, T, ldt, nt, eps)
+        if (C <= 64) { SEP_CLS(1); } else if (C <= 128) { SEP_CLS(2); } else if (C <= 256) { SEP_CLS(4); } else { SEP_CLS(8); }
 #undef SEP_CLS
         SEP_CHECK_LAUNCH("sep_cln_stats");
         return 0;
     }
+    sep_set_kernel("cln_three_stats");
     hipLaunchKernelGGL((cln_colsums_kernel<false>), dim3(ceil_div(T, CLN_TCOLS), B), dim3(256), 0, stream, x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, alpha, ws, C, T, ldt);
     hipLaunchKernelGGL(cln_scan_fwd_kernel, dim3(B), dim3(1024), 0, stream, (const double*)ws, mean, rstd, C, T, ldt, eps);
     SEP_CHECK_LAUNCH("sep_cln_stats");
@@ -643,15 +645,16 @@ extern "C" int sep_cln_bwd(const float* dy, const float* x, const float* gamma, 
         SEP_REQUIRE((long)B * nt <= 0x7fffffffL / 4, "sep_cln_bwd: too many tiles");
         const ChainWs cw = chain_ws(ws, B, C, nt);
         SEP_REQUIRE(hipMemsetAsync(ws, 0, cw.clear_bytes, stream) == hipSuccess, "sep_cln: clearing the chain records failed");
-#define SEP_CLB(RR, NW) hipLaunchKernelGGL((cln_chain_bwd_kernel<RR, NW>), dim3(B * nt), dim3(64 * NW), 0, stream, dy, x, mean, rstd, gamma, alpha, dx, cw.parts, cw.ticket, cw.agg, cw.incl, B, C, T, ldt, nt, eps)
+#define SEP_CLB(RR, NW) sep_set_kernel("cln_chain_bwd<" #RR "," #NW ">"); hipLaunchKernelGGL((cln_chain_bwd_kernel<RR, NW>), dim3(B * nt), dim3(64 * NW), 0, stream, dy, x, mean, rstd, gamma, alpha, dx, cw.parts, cw.ticket, cw.agg, cw.incl, B, C, T, ldt, nt, eps)
         // C > 256: 8 waves x 8 rounds (124 registers: two workgroups per compute unit, one walks its chain while the other streams) beat
         // 16 waves x 4 rounds (88 registers but one workgroup per CU): 118 against 143 us at B = 16, C = 512 (profiles/r05ze_cln_chain.txt)
-        if (C <= 64) SEP_CLB(1, 8); else if (C <= 128) SEP_CLB(2, 8); else if (C <= 256) SEP_CLB(4, 8); else SEP_CLB(8, 8);
+        if (C <= 64) { SEP_CLB(1, 8); } else if (C <= 128) { SEP_CLB(2, 8); } else if (C <= 256) { SEP_CLB(4, 8); } else { SEP_CLB(8, 8); }
 #undef SEP_CLB
         hipLaunchKernelGGL(cln_chain_parts_kernel, dim3(ceil_div(C, 64), 3, B), dim3(1024), 0, stream, (const float*)cw.parts, dgamma_part, dbeta_part, dalpha_part, B, C, nt);
         SEP_CHECK_LAUNCH("sep_cln_bwd");
         return 0;
     }
+    sep_set_kernel("cln_three_bwd");
     hipLaunchKernelGGL((cln_colsums_kernel<true>), dim3(ceil_div(T, CLN_TCOLS), B), dim3(256), 0, stream, x, dy, gamma, mean, alpha, ws, C, T, ldt);
     hipLaunchKernelGGL(cln_scan_bwd_kernel, dim3(B), dim3(1024), 0, stream, ws, mean, rstd, C, T, ldt, eps);
     hipLaunchKernelGGL(cln_apply_bwd_kernel, dim3(ceil_div(C, 4), B), dim3(256), 0, stream, dy, x, mean, rstd, (const double*)ws, gamma, alpha, dx, dgamma_part, dbeta_part, dalpha_part, C, T, ldt);

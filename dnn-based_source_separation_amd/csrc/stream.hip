@@ -1601,15 +1601,19 @@ extern "C" int sep_encoder_fwd(const float* x, const float* E, float* w, double*
     const size_t smem = (size_t)Cin * span * sizeof(float);
     SEP_REQUIRE(smem <= 150 * 1024, "sep_encoder_fwd: Cin*(128*S+L-S) floats exceed LDS (Cin=%d L=%d S=%d)", Cin, L, S);
     if (Cin == 1 && L == 16 && S == 8 && B <= 65535) {
+        sep_set_kernel("encoder_l16s8");
         hipLaunchKernelGGL(encoder_fwd_l16s8_kernel, dim3(ceil_div(ldt, 256), B), dim3(256), 0, (hipStream_t)stream, x, E, w, stats, Tin, N, F, ldt, pad_left, relu);
         SEP_CHECK_LAUNCH("sep_encoder_fwd");
         return 0;
     }
     dim3 grid(ldt / ENC_FT, B);
-    if (Cin * L == 16)
+    if (Cin * L == 16) {
+        sep_set_kernel("encoder<16>");
         hipLaunchKernelGGL(encoder_fwd_kernel<16>, grid, dim3(256), smem, (hipStream_t)stream, x, E, w, stats, B, Cin, Tin, N, L, S, F, ldt, pad_left, relu);
-    else
+    } else {
+        sep_set_kernel("encoder<0>");
         hipLaunchKernelGGL(encoder_fwd_kernel<0>, grid, dim3(256), smem, (hipStream_t)stream, x, E, w, stats, B, Cin, Tin, N, L, S, F, ldt, pad_left, relu);
+    }
     SEP_CHECK_LAUNCH("sep_encoder_fwd");
     return 0;
 }
@@ -1637,6 +1641,7 @@ extern "C" int sep_dwconv_fwd(const float* a, const double* stats1, const float*
         const int rows = C % 2 == 0 ? 2 : 1;
         const dim3 grid((unsigned)((long)B * C / rows));
 #define SEP_DWF(DM) do { \
+            sep_set_kernel(rows == 2 ? "dwconv_fwd_direct<" #DM ",2>" : "dwconv_fwd_direct<" #DM ",1>"); \
             if (rows == 2) hipLaunchKernelGGL((dwconv_fwd_direct_kernel<DM, 2>), grid, dim3(256), 0, (hipStream_t)stream, a, stats1, gamma1, beta1, alpha1, wd, bd, alpha2, z, stats2, C, T, ldt, dilation, eps); \
             else hipLaunchKernelGGL((dwconv_fwd_direct_kernel<DM, 1>), grid, dim3(256), 0, (hipStream_t)stream, a, stats1, gamma1, beta1, alpha1, wd, bd, alpha2, z, stats2, C, T, ldt, dilation, eps); \
         } while (0)
@@ -1650,6 +1655,7 @@ extern "C" int sep_dwconv_fwd(const float* a, const double* stats1, const float*
     const int dpad = (dilation + 3) & ~3;
     const size_t smem = 4 * (size_t)(DW_TT + 2 * dpad) * sizeof(float);
     const long total = (long)B * C * ceil_div(ldt, DW_TT);
+    sep_set_kernel("dwconv_fwd_tiles");
     hipLaunchKernelGGL(dwconv_fwd_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), smem, (hipStream_t)stream, a, stats1, gamma1, beta1, alpha1, wd, bd, alpha2, z, stats2, B, C, T, ldt, dilation, dpad, eps);
     SEP_CHECK_LAUNCH("sep_dwconv_fwd");
     return 0;
@@ -1671,7 +1677,8 @@ extern "C" int sep_dwconv_bwd(const float* dv2, const float* z, const float* a, 
         const size_t rsmem = (size_t)ldt * sizeof(float);      // (the recomputing form's v1 row and the dz row share it)
         const dim3 grid((unsigned)((long)B * C));
 #define SEP_DWB(AL, NIT, RC) hipLaunchKernelGGL((dwconv_bwd_row_kernel<AL, NIT, RC>), grid, dim3(256), rsmem, (hipStream_t)stream, dv2, z, bd, a, stats1, gamma1, beta1, alpha1, stats2, gamma2, alpha2, bsum2, wd, dv1, rowpart, bacc1, arrive1, bsum1, C, T, ldt, dilation, eps)
-#define SEP_DWB2(AL, NIT) do { if (recomp) SEP_DWB(AL, NIT, true); else SEP_DWB(AL, NIT, false); } while (0)
+#define SEP_DWB2(AL, NIT) do { sep_set_kernel(recomp ? "dwconv_bwd_row<" #AL "," #NIT ",true>" : "dwconv_bwd_row<" #AL "," #NIT ",false>"); \
+                               if (recomp) SEP_DWB(AL, NIT, true); else SEP_DWB(AL, NIT, false); } while (0)
         const int dm = dilation % 4 == 0 ? 0 : dilation <= 2 ? dilation : 3;
         if (dm == 0) { if (ldt <= 4096) SEP_DWB2(0, 4); else SEP_DWB2(0, 8); }
         else if (dm == 1) { if (ldt <= 4096) SEP_DWB2(1, 4); else SEP_DWB2(1, 8); }
@@ -1685,6 +1692,7 @@ extern "C" int sep_dwconv_bwd(const float* dv2, const float* z, const float* a, 
     const int dpad = (dilation + 3) & ~3;
     const size_t smem = 4 * 2 * (size_t)(DW_TT + 2 * dpad) * sizeof(float);
     const long total = (long)B * C * ceil_div(ldt, DW_TT);
+    sep_set_kernel("dwconv_bwd_tiles");
     hipLaunchKernelGGL(dwconv_bwd_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), smem, (hipStream_t)stream, dv2, z, a, stats1, gamma1, beta1, alpha1, stats2, gamma2, alpha2, bsum2, wd, dv1, rowpart, bacc1, arrive1, bsum1, B, C, T, ldt, dilation, dpad, eps);
     SEP_CHECK_LAUNCH("sep_dwconv_bwd");
     return 0;
@@ -1840,6 +1848,7 @@ extern "C" int sep_decoder_fwd(const float* w, const float* m, const float* D, f
         // est is completed by stores and by two-addend atomic adds at the tile seams: it starts from zero
         SEP_REQUIRE(hipMemsetAsync(est, 0, (size_t)B * n_src * Tout * sizeof(float), (hipStream_t)stream) == hipSuccess, "sep_decoder_fwd: memset failed");
         const dim3 g16(ldt / 64, B);
+        sep_set_kernel(n_src <= 2 ? "decoder_fwd16<2>" : "decoder_fwd16<4>");
         if (n_src <= 2) hipLaunchKernelGGL(decoder_fwd16_kernel<2>, g16, dim3(256), 0, (hipStream_t)stream, w, m, D, est, latent, n_src, N, F, ldt, Tout, pad_left);
         else hipLaunchKernelGGL(decoder_fwd16_kernel<4>, g16, dim3(256), 0, (hipStream_t)stream, w, m, D, est, latent, n_src, N, F, ldt, Tout, pad_left);
         SEP_CHECK_LAUNCH("sep_decoder_fwd");
@@ -1849,6 +1858,7 @@ extern "C" int sep_decoder_fwd(const float* w, const float* m, const float* D, f
     SEP_REQUIRE(FB > 0, "sep_decoder_fwd: kernel_size / stride too large");
     dim3 grid(ceil_div(ldt + R - 1, FB), B * n_src);
     const size_t smem = (size_t)256 * (LC + 1) * sizeof(float);
+    sep_set_kernel(LC == 16 ? "decoder_fwd<16>" : "decoder_fwd<0>");
     if (LC == 16)
         hipLaunchKernelGGL(decoder_fwd_kernel<16>, grid, dim3(256), smem, (hipStream_t)stream, w, m, D, est, latent, n_src, N, Cout, L, S, F, ldt, Tout, pad_left);
     else
@@ -1865,6 +1875,11 @@ extern "C" int sep_decoder_bwd(const float* d_est, const float* w, const float* 
     const int nz = N >= 64 ? 8 : 1;                               // 2048 workgroups at paper-best instead of 256
     dim3 grid(ceil_div(ldt, 256), B, nz);
     const int LC = Cout * L;
+#define SEP_DEB(NAME) sep_set_kernel(nz == 8 ? NAME "/nz8" : NAME "/nz1")
+    if (LC == 16 && n_src <= 2) SEP_DEB("decoder_bwd<16,2>");
+    else if (LC == 16 && n_src <= 4) SEP_DEB("decoder_bwd<16,4>");
+    else SEP_DEB("decoder_bwd<0,0>");
+#undef SEP_DEB
     if (LC == 16 && n_src <= 2)
         hipLaunchKernelGGL((decoder_bwd_kernel<16, 2>), grid, dim3(256), 0, (hipStream_t)stream, d_est, w, m, D, dpre, dwm, n_src, N, Cout, L, S, F, ldt, Tout, pad_left, raw_mask);
     else if (LC == 16 && n_src <= 4)
@@ -1902,9 +1917,11 @@ extern "C" int sep_gln_tokens_fwd(const float* x, const float* gamma, const floa
     const int ns = gln_tokens_nsplit(nseq, (long)L * C);
     if (ns > 1) {
         SEP_REQUIRE(ws != nullptr, "sep_gln_tokens_fwd: this shape needs the workspace of sep_gln_tokens_ws_bytes");
+        sep_set_kernel("gln_tokens_fwd/sliced");
         hipLaunchKernelGGL(gln_tokens_part_fwd_kernel, dim3(ns, nseq), dim3(256), 0, (hipStream_t)stream, x, (double*)ws, L * C, ns);
         hipLaunchKernelGGL(gln_tokens_apply_fwd_kernel, dim3(ns, nseq), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, (const double*)ws, y, stats, L * C, ns, C, eps);
     } else {
+        sep_set_kernel("gln_tokens_fwd");
         hipLaunchKernelGGL(gln_tokens_fwd_kernel, dim3((unsigned)nseq), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, stats, L * C, C, eps);
     }
     SEP_CHECK_LAUNCH("sep_gln_tokens_fwd");
@@ -1920,9 +1937,11 @@ extern "C" int sep_gln_tokens_bwd(const float* dy, const float* x, const float* 
         SEP_REQUIRE(ws != nullptr, "sep_gln_tokens_bwd: this shape needs the workspace of sep_gln_tokens_ws_bytes");
         double* wsd = (double*)ws;
         float* wsf = (float*)(wsd + (size_t)nseq * ns * 2);
+        sep_set_kernel("gln_tokens_bwd/sliced");
         hipLaunchKernelGGL(gln_tokens_part_bwd_kernel, dim3(ns, nseq), dim3(256), 0, (hipStream_t)stream, dy, x, gamma, stats, wsd, wsf, L * C, ns, C);
         hipLaunchKernelGGL(gln_tokens_apply_bwd_kernel, dim3(ns, nseq), dim3(256), 0, (hipStream_t)stream, dy, x, gamma, stats, (const double*)wsd, (const float*)wsf, dx, part, L * C, ns, C);
     } else {
+        sep_set_kernel("gln_tokens_bwd");
         hipLaunchKernelGGL(gln_tokens_bwd_kernel, dim3((unsigned)nseq), dim3(256), 0, (hipStream_t)stream, dy, x, gamma, stats, dx, part, L * C, C);
     }
     SEP_CHECK_LAUNCH("sep_gln_tokens_bwd");
@@ -2016,11 +2035,13 @@ extern "C" int sep_depthwise_fwd(const float* x, const float* w, const float* bi
         // the LDS row is only touched when a tap's shift is not a multiple of 4 frames (the kernel's `aligned`): none is asked for otherwise,
         // which is every dilation >= 4 of the TCN -- 128 KB per workgroup at the longest row would leave one workgroup per compute unit
         const bool al = ((pad | (dil - pad) | (2 * dil - pad)) & 3) == 0;
+        sep_set_kernel(al ? "depthwise3_row<0>/aligned" : "depthwise3_row<0>/lds");
         hipLaunchKernelGGL((depthwise3_row_kernel<0>), dim3((unsigned)((long)B * C)), dim3(256), al ? (size_t)0 : (size_t)Tin * sizeof(float), (hipStream_t)stream, x, w, bias, y, C, Tin, dil, pad);
         SEP_CHECK_LAUNCH("sep_depthwise_fwd");
         return 0;
     }
     SEP_REQUIRE((long)B * C <= 65535, "sep_depthwise_fwd: B*C too large");
+    sep_set_kernel("depthwise_fwd");
     hipLaunchKernelGGL(depthwise_fwd_kernel, dim3(ceil_div(Tout, 256), B * C), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, C, Tin, Tout, Kw, stride, pad, dil);
     SEP_CHECK_LAUNCH("sep_depthwise_fwd");
     return 0;
@@ -2031,11 +2052,13 @@ extern "C" int sep_depthwise_bwd_input(const float* dy, const float* w, float* d
     SEP_REQUIRE(dy && w && dx && B > 0 && C > 0 && stride > 0, "sep_depthwise_bwd_input: bad arguments");
     if (depthwise3_rows(Tin, Tout, Kw, stride)) {
         const bool al = ((pad | (pad - dil) | (pad - 2 * dil)) & 3) == 0;          // (see sep_depthwise_fwd)
+        sep_set_kernel(al ? "depthwise3_row<1>/aligned" : "depthwise3_row<1>/lds");
         hipLaunchKernelGGL((depthwise3_row_kernel<1>), dim3((unsigned)((long)B * C)), dim3(256), al ? (size_t)0 : (size_t)Tin * sizeof(float), (hipStream_t)stream, dy, w, (const float*)nullptr, dx, C, Tin, dil, pad);
         SEP_CHECK_LAUNCH("sep_depthwise_bwd_input");
         return 0;
     }
     SEP_REQUIRE((long)B * C <= 65535, "sep_depthwise_bwd_input: B*C too large");
+    sep_set_kernel("depthwise_bwd_input");
     hipLaunchKernelGGL(depthwise_bwd_input_kernel, dim3(ceil_div(Tin, 256), B * C), dim3(256), 0, (hipStream_t)stream, dy, w, dx, C, Tin, Tout, Kw, stride, pad, dil);
     SEP_CHECK_LAUNCH("sep_depthwise_bwd_input");
     return 0;
@@ -2045,10 +2068,12 @@ extern "C" int sep_depthwise_bwd_weight(const float* dy, const float* x, float* 
                                         int stride, int pad, int dil, sep_stream_t stream) {
     SEP_REQUIRE(dy && x && partial && B > 0 && C > 0, "sep_depthwise_bwd_weight: bad arguments");
     if (depthwise3_rows(Tin, Tout, Kw, stride)) {
+        sep_set_kernel("depthwise3_wgrad_row");
         hipLaunchKernelGGL(depthwise3_wgrad_row_kernel, dim3((unsigned)((long)B * C)), dim3(256), (size_t)Tin * sizeof(float), (hipStream_t)stream, dy, x, partial, Tin, dil, pad);
         SEP_CHECK_LAUNCH("sep_depthwise_bwd_weight");
         return 0;
     }
+    sep_set_kernel("depthwise_bwd_weight");
     hipLaunchKernelGGL(depthwise_bwd_weight_kernel, dim3(B * C), dim3(256), 0, (hipStream_t)stream, dy, x, partial, C, Tin, Tout, Kw, stride, pad, dil);
     SEP_CHECK_LAUNCH("sep_depthwise_bwd_weight");
     return 0;
@@ -2141,6 +2166,7 @@ extern "C" int sep_split_rows(const float* x, void* out, int32_t* exps, float* s
     SEP_REQUIRE(x && out && exps && B > 0 && C > 0 && T > 0 && ldt >= T && ldt % 128 == 0 && ldt <= 8192, "sep_split_rows: bad sizes (ldt <= 8192)");
     SEP_REQUIRE(k >= 1 && k <= SPLIT_MAXK && ldt % (32 * k) == 0 && (long)B * C <= 0x7fffffffL, "sep_split_rows: k = %d must divide ldt / 32 (<= %d)", k, SPLIT_MAXK);
     const dim3 grid((unsigned)((long)B * C));
+    sep_set_kernel(ldt <= 4096 ? "split_rows<4>" : "split_rows<8>");
     if (ldt <= 4096) hipLaunchKernelGGL(split_rows_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, reinterpret_cast<unsigned*>(out), exps, sums, C, T, ldt, k);
     else hipLaunchKernelGGL(split_rows_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, x, reinterpret_cast<unsigned*>(out), exps, sums, C, T, ldt, k);
     SEP_CHECK_LAUNCH("sep_split_rows");

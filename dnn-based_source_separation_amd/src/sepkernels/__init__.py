@@ -432,8 +432,10 @@ def _check(rc, name):
 
 
 def last_kernel():
-    """Name of the kernel instance this thread's last pw_gemm / pw_wgrad / pw_wgrad_batch launch went to (sep_last_kernel: family and
-    template arguments, e.g. 'pc<4,1,SEP_PRO_GLN_PRELU,false,SEP_EPI_RESIDUAL>'), '' before the first one.  Not a launch: never recorded."""
+    """Name of the kernel instance this thread's last pw_gemm / pw_wgrad / pw_wgrad_batch launch, or its last call of a streaming dispatcher
+    (encoder_fwd, dwconv_fwd / _bwd, decoder_fwd / _bwd, depthwise_*, split_rows, gln_tokens_*, cln_*, depthwise_cln_*), went to
+    (sep_last_kernel: family and template arguments, e.g. 'pc<4,1,SEP_PRO_GLN_PRELU,false,SEP_EPI_RESIDUAL>', 'dwconv_bwd_row<3,8,true>',
+    'decoder_bwd<16,2>/nz1'), '' before the first one.  Not a launch: never recorded."""
     return load().sep_last_kernel().decode()
 
 

@@ -39,17 +39,32 @@ typedef void* sep_stream_t; /* hipStream_t */
 
 int sep_version(void);
 const char* sep_last_error(void);
-/* Which kernel instance the calling thread's last sep_pw_gemm / sep_pw_wgrad / sep_pw_wgrad_batch launch went to: a string literal
- * naming the family and the template arguments as the dispatcher spells them, "" before the first such launch.  The families:
+/* Which kernel instance the calling thread's last sep_pw_gemm / sep_pw_wgrad / sep_pw_wgrad_batch launch, or its last launch through one
+ * of the streaming dispatchers listed below, went to: a string literal naming the family and the template arguments as the dispatcher
+ * spells them, "" before the first such launch.  The GEMM families:
  *   pc<WR,WC,prologue,two-source,epilogue>         producer / consumer kernel, packed weights (csrc/gemm_pc.hip)
  *   coop<MI,prologue,two-source,epilogue,ns=N>     cooperative kernel, packed weights (csrc/gemm_coop.hip)
  *   direct<trans_a,prologue,two-source,epilogue,arith=A>   per-wave kernel, flags compile-time (csrc/gemm.hip)
  *   direct_rt<trans_a,prologue,two-source>         the same kernel with the epilogue flags read at run time
  *   staged                                         register-staged fallback
  *   wgrad_pc16<..> / wgrad_pc16_pre<..> / wgrad_pc16_batch<..> / wgrad_pc<..> / wgrad_split<..> / wgrad_direct<..> / wgrad
- * e.g. "pc<4,1,SEP_PRO_GLN_PRELU,false,SEP_EPI_RESIDUAL>".  Thread-local like sep_last_error; one pointer store per launch, no device
+ * e.g. "pc<4,1,SEP_PRO_GLN_PRELU,false,SEP_EPI_RESIDUAL>".  The streaming dispatchers (csrc/stream.hip, cln.hip, causal.hip) name the kernel
+ * function and its template arguments as spelled at the launch; a run-time value that selects behaviour without a template argument
+ * follows a "/":
+ *   sep_encoder_fwd                   encoder_l16s8 | encoder<16> | encoder<0>
+ *   sep_dwconv_fwd                    dwconv_fwd_direct<DM,ROWS> | dwconv_fwd_tiles
+ *   sep_dwconv_bwd                    dwconv_bwd_row<AL,NIT,recompute> | dwconv_bwd_tiles
+ *   sep_decoder_fwd                   decoder_fwd16<2|4> | decoder_fwd<16|0>
+ *   sep_decoder_bwd                   decoder_bwd<16,2|16,4|0,0>/nz1|nz8        (nz: slices of the basis rows, the grid's z)
+ *   sep_depthwise_fwd / _bwd_input    depthwise3_row<0|1>/aligned|lds | depthwise_fwd | depthwise_bwd_input
+ *   sep_depthwise_bwd_weight          depthwise3_wgrad_row | depthwise_bwd_weight
+ *   sep_split_rows                    split_rows<4|8>
+ *   sep_gln_tokens_fwd / _bwd         gln_tokens_fwd[/sliced] | gln_tokens_bwd[/sliced]
+ *   sep_cln_fwd / _stats / _bwd       cln_chain_fwd<RR,true|false> | cln_chain_bwd<RR,8> | cln_three_fwd | cln_three_stats | cln_three_bwd
+ *   sep_depthwise_cln_fwd / _bwd_weight   cd_depthwise_fwd<KW,staged> | cd_depthwise_wgrad<KW,staged>
+ * Every other entry point leaves the name as it was.  Thread-local like sep_last_error; one pointer store per launch, no device
  * work; takes no stream, so it is not a sequence op.  For tests and tools that must know which instance a shape reaches
- * (tests/gemm_matrix.py); additive to ABI 23. */
+ * (tests/gemm_matrix.py, tests/stream_matrix.py); additive to ABI 23. */
 const char* sep_last_kernel(void);
 
 /* ---- prologue modes applied to the X operand while it is staged into LDS ---------- */

@@ -740,7 +740,7 @@ def test_reduce_slabs_and_f64():
 
 
 # ------------------------------------------------------------------------------------------- depthwise
-@pytest.mark.parametrize("T,d", [(3999, 1), (3999, 2), (3999, 128), (300, 8), (1030, 64), (2100, 256)])
+@pytest.mark.parametrize("T,d", [(3999, 1), (3999, 2), (3999, 128), (300, 8), (1030, 64), (2100, 256), (4100, 3), (100, 128)])      # the last two: NIT = 8, any-d neighbours and the LDS forward; T < d
 def test_dwconv_fwd_bwd(T, d):
     B, C = 2, 8
     ldt = (T + 127) // 128 * 128
