@@ -1617,8 +1617,13 @@ extern "C" int sep_pw_gemm(const sep_gemm_desc* d, sep_stream_t stream) {
         // curated combinations exist in both arithmetics (GLN_BWD: fp32 MFMA only -- its time is the prologue, measured equal)
         const bool split3 = d->arith == SEP_ARITH_F16X3 && d->a_amax != nullptr;
         const bool split6 = d->arith == SEP_ARITH_BF16X6 || d->arith == SEP_ARITH_F16X3;
-#define SEP_LD(T, P, S, E)                                                                                                                           \
-    do {                                                                                                                                             \
+        // 1. the fused products of the Conv-TasNet step (gemm_common.hpp: one row each), epilogue flags compile-time
+        const int ef = d->epi_flags, pm = d->pro_mode;
+        const bool tr = d->trans_a != 0, sp = d->k_split != 0;
+        bool done = false;
+#define SEP_LD(T, P, S, E, MI4)                                                                                                                      \
+    if (tr == T && sp == S && pm == P && ef == (E)) {                                                                                                \
+        done = true;                                                                                                                                 \
         if (split3 && P != SEP_PRO_GLN_BWD) {                                                                                                        \
             sep_set_kernel("direct<" #T "," #P "," #S "," #E ",arith=2>");                                                                           \
             hipLaunchKernelGGL((pw_gemm_direct_kernel<T, P, S, E, (P != SEP_PRO_GLN_BWD ? 2 : 0)>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d); \
@@ -1629,58 +1634,34 @@ extern "C" int sep_pw_gemm(const sep_gemm_desc* d, sep_stream_t stream) {
             sep_set_kernel("direct<" #T "," #P "," #S "," #E ",arith=0>");                                                                           \
             hipLaunchKernelGGL((pw_gemm_direct_kernel<T, P, S, E, 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);                           \
         }                                                                                                                                            \
-    } while (0)
-        // 1. the (operand form, prologue, split, epilogue) combinations of the Conv-TasNet step, epilogue flags compile-time
-        const int ef = d->epi_flags, pm = d->pro_mode;
-        const bool tr = d->trans_a != 0, sp = d->k_split != 0;
-        bool done = true;
-        if (d->M % BM != 0) done = false;          // the specialised epilogues have no row predicate
-        else if (!tr && !sp && pm == SEP_PRO_NONE && ef == SEP_EPI_STATS_PRELU) SEP_LD(false, SEP_PRO_NONE, false, SEP_EPI_STATS_PRELU);              // TCN conv1
-        else if (!tr && !sp && pm == SEP_PRO_GLN_PRELU && ef == SEP_EPI_RESIDUAL) SEP_LD(false, SEP_PRO_GLN_PRELU, false, SEP_EPI_RESIDUAL);     // heads
-        else if (!tr && !sp && pm == SEP_PRO_GLN_PRELU && ef == 0) SEP_LD(false, SEP_PRO_GLN_PRELU, false, 0);                                   // last layer: skip head only
-        else if (!tr && !sp && pm == SEP_PRO_PRELU && ef == SEP_EPI_SIGMOID) SEP_LD(false, SEP_PRO_PRELU, false, SEP_EPI_SIGMOID);               // mask
-        else if (!tr && !sp && pm == SEP_PRO_PRELU && ef == 0) SEP_LD(false, SEP_PRO_PRELU, false, 0);                                           // mask without its activation (softmax over channels, staged layers)
-        else if (!tr && !sp && pm == SEP_PRO_GLN && ef == 0) SEP_LD(false, SEP_PRO_GLN, false, 0);                                               // bottleneck
-        else if (!tr && !sp && pm == SEP_PRO_NONE && ef == 0) SEP_LD(false, SEP_PRO_NONE, false, 0);                                             // plain 1x1 conv
-        else if (!tr && !sp && pm == SEP_PRO_NONE && ef == SEP_EPI_RESIDUAL) SEP_LD(false, SEP_PRO_NONE, false, SEP_EPI_RESIDUAL);               // heads of the staged (causal) layers: input already normalised
-        else if (tr && sp && pm == SEP_PRO_NONE && ef == 0) SEP_LD(true, SEP_PRO_NONE, true, 0);                                                 // ... and their heads^T
-        else if (tr && !sp && pm == SEP_PRO_NONE && ef == 0) SEP_LD(true, SEP_PRO_NONE, false, 0);                                               // plain input gradient
-        else if (tr && !sp && pm == SEP_PRO_NONE && ef == SEP_EPI_PRELU_BWD) SEP_LD(true, SEP_PRO_NONE, false, SEP_EPI_PRELU_BWD);               // mask^T
-        else if (tr && sp && pm == SEP_PRO_NONE && ef == (SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU)) SEP_LD(true, SEP_PRO_NONE, true, SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU);   // heads^T
-        else if (tr && !sp && pm == SEP_PRO_NONE && ef == (SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU)) SEP_LD(true, SEP_PRO_NONE, false, SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU);
-        else if (tr && !sp && pm == SEP_PRO_NONE && ef == SEP_EPI_ROWSUMS) SEP_LD(true, SEP_PRO_NONE, false, SEP_EPI_ROWSUMS);                   // bottleneck^T
-        else if (tr && !sp && pm == SEP_PRO_GLN_BWD && ef == SEP_EPI_RESIDUAL) SEP_LD(true, SEP_PRO_GLN_BWD, false, SEP_EPI_RESIDUAL);           // conv1^T
-        else if (tr && !sp && pm == SEP_PRO_GLN_BWD && ef == 0) SEP_LD(true, SEP_PRO_GLN_BWD, false, 0);
-        else done = false;
-        // 2. anything else: same kernels with the flags read at run time
-        if (!done) {
-            // (NAME: the arguments as the caller spelled them -- macro arguments that pass through SEP_LAUNCH_DIRECT arrive here expanded)
-#define SEP_LG(T, P, S, NAME)                                                                                                     \
-    do {                                                                                                                          \
-        sep_set_kernel("direct_rt<" NAME "," #S ">");                                                                             \
-        hipLaunchKernelGGL((pw_gemm_direct_kernel<T, P, S, -1, 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);            \
-    } while (0)
-#define SEP_LAUNCH_DIRECT(T, P)                       \
-    do {                                              \
-        if (sp) SEP_LG(T, P, true, #T "," #P);        \
-        else SEP_LG(T, P, false, #T "," #P);          \
-    } while (0)
-            switch (pm * 2 + (tr ? 1 : 0)) {
-                case 0: SEP_LAUNCH_DIRECT(false, SEP_PRO_NONE); break;
-                case 1: SEP_LAUNCH_DIRECT(true, SEP_PRO_NONE); break;
-                case 2: SEP_LAUNCH_DIRECT(false, SEP_PRO_PRELU); break;
-                case 3: SEP_LAUNCH_DIRECT(true, SEP_PRO_PRELU); break;
-                case 4: SEP_LAUNCH_DIRECT(false, SEP_PRO_GLN); break;
-                case 5: SEP_LAUNCH_DIRECT(true, SEP_PRO_GLN); break;
-                case 6: SEP_LAUNCH_DIRECT(false, SEP_PRO_GLN_PRELU); break;
-                case 7: SEP_LAUNCH_DIRECT(true, SEP_PRO_GLN_PRELU); break;
-                case 8: SEP_LG(false, SEP_PRO_GLN_BWD, false, "false,SEP_PRO_GLN_BWD"); break;
-                default: SEP_LG(true, SEP_PRO_GLN_BWD, false, "true,SEP_PRO_GLN_BWD"); break;
-            }
-#undef SEP_LAUNCH_DIRECT
-#undef SEP_LG
+    }
+        if (d->M % BM == 0) {                      // the specialised epilogues have no row predicate
+            SEP_FUSED_COMBOS(SEP_LD, SEP_LD)
         }
 #undef SEP_LD
+        // 2. anything else: same kernels with the flags read at run time, one row per prologue (gemm_common.hpp).  A prologue without a
+        // two-source form (TWO = 0; the argument checks above refuse k_split with it) names its one-source instance in both branches.
+        if (!done) {
+            // (NAME: the arguments as SEP_LRT spells them -- P has passed through SEP_LRT when it arrives here, expanded to its number)
+#define SEP_LG(T, P, S, NAME)                                                                                                     \
+    do {                                                                                                                          \
+        sep_set_kernel("direct_rt<" NAME ">");                                                                                    \
+        hipLaunchKernelGGL((pw_gemm_direct_kernel<T, P, S, -1, 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);            \
+    } while (0)
+#define SEP_LRT(P, TWO)                                                                \
+    if (pm == P) {                                                                     \
+        if (TWO && sp) {                                                               \
+            if (tr) SEP_LG(true, P, (TWO != 0), "true," #P ",true");                   \
+            else SEP_LG(false, P, (TWO != 0), "false," #P ",true");                    \
+        } else {                                                                       \
+            if (tr) SEP_LG(true, P, false, "true," #P ",false");                       \
+            else SEP_LG(false, P, false, "false," #P ",false");                        \
+        }                                                                              \
+    }
+            SEP_GEMM_PROLOGUES(SEP_LRT)
+#undef SEP_LRT
+#undef SEP_LG
+        }
     } else {
         sep_set_kernel("staged");
         hipLaunchKernelGGL(pw_gemm_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);
@@ -1717,25 +1698,22 @@ extern "C" int sep_pw_wgrad(const sep_wgrad_desc* d, sep_stream_t stream) {
         return 0;
     }
     if (direct_ok && d->arith != SEP_ARITH_F32) {      // F16X3: the weight gradient stays on the bf16 split (both operands are activations)
-#define SEP_LWG(KERNEL, FAMILY, XM, THREADS)                                                                    \
-    do {                                                                                                        \
-        sep_set_kernel(FAMILY "<" #XM ">");                                                                     \
-        hipLaunchKernelGGL((KERNEL<XM>), dim3(grid), dim3(THREADS), 0, (hipStream_t)stream, *d);                \
-    } while (0)
-        switch (d->x_mode) {
-            case SEP_PRO_NONE: SEP_LWG(pw_wgrad_split_kernel, "wgrad_split", SEP_PRO_NONE, 256); break;
-            case SEP_PRO_PRELU: SEP_LWG(pw_wgrad_split_kernel, "wgrad_split", SEP_PRO_PRELU, 256); break;
-            case SEP_PRO_GLN: SEP_LWG(pw_wgrad_split_kernel, "wgrad_split", SEP_PRO_GLN, 256); break;
-            default: SEP_LWG(pw_wgrad_split_kernel, "wgrad_split", SEP_PRO_GLN_PRELU, 256); break;
-        }
+        // one case per prologue (SEP_WGRAD_XMODES, gemm_common.hpp; x_mode was range-checked above)
+#define SEP_LWS(XM)                                                                                                 \
+    case XM:                                                                                                        \
+        sep_set_kernel("wgrad_split<" #XM ">");                                                                     \
+        hipLaunchKernelGGL((pw_wgrad_split_kernel<XM>), dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);         \
+        break;
+        switch (d->x_mode) { SEP_WGRAD_XMODES(SEP_LWS) }
+#undef SEP_LWS
     } else if (direct_ok) {
-        switch (d->x_mode) {
-            case SEP_PRO_NONE: SEP_LWG(pw_wgrad_direct_kernel, "wgrad_direct", SEP_PRO_NONE, 512); break;
-            case SEP_PRO_PRELU: SEP_LWG(pw_wgrad_direct_kernel, "wgrad_direct", SEP_PRO_PRELU, 512); break;
-            case SEP_PRO_GLN: SEP_LWG(pw_wgrad_direct_kernel, "wgrad_direct", SEP_PRO_GLN, 512); break;
-            default: SEP_LWG(pw_wgrad_direct_kernel, "wgrad_direct", SEP_PRO_GLN_PRELU, 512); break;
-        }
-#undef SEP_LWG
+#define SEP_LWD(XM)                                                                                                 \
+    case XM:                                                                                                        \
+        sep_set_kernel("wgrad_direct<" #XM ">");                                                                    \
+        hipLaunchKernelGGL((pw_wgrad_direct_kernel<XM>), dim3(grid), dim3(512), 0, (hipStream_t)stream, *d);        \
+        break;
+        switch (d->x_mode) { SEP_WGRAD_XMODES(SEP_LWD) }
+#undef SEP_LWD
     } else {
         sep_set_kernel("wgrad");
         hipLaunchKernelGGL(pw_wgrad_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *d);
@@ -1755,10 +1733,13 @@ extern "C" int sep_pw_wgrad_batch(const sep_wgrad_desc* ds, int n, sep_stream_t 
                a.x_beta == b.x_beta && (a.G2 == nullptr) == (b.G2 == nullptr) && (a.partial_bias == nullptr) == (b.partial_bias == nullptr);
     }
     SEP_REQUIRE(same, "sep_pw_wgrad_batch: the products must agree in everything but G, G2, X, partial, partial_bias");
-    // one grid for all of them where the producer / consumer fp16 kernel takes the shape (checked like sep_pw_wgrad does, on the first)
+    // one grid for all of them where the producer / consumer fp16 kernel takes the shape.  Checked on the first: sep_pw_wgrad's argument
+    // checks restated as a condition (a descriptor it would refuse goes to it below and is refused there), then the kernel family's own
+    // rule inside sep_pw_wgrad_pc16_batch -- arithmetic, g_mul, x_div, tile shapes and the slab bound.  That rule bounds nsplit in 16-frame
+    // chunks where sep_pw_wgrad's argument check counts 32-frame ones (WK); the check is not restated here, so that the batched grid is
+    // taken for exactly the descriptors it always was.
     const sep_wgrad_desc* d = &ds[0];
     const bool plain_ok = d->B > 0 && d->M > 0 && d->N > 0 && d->T > 0 && d->ldt % 128 == 0 && d->ldt >= d->T && d->nsplit > 0 &&
-                          (long)d->nsplit <= (long)d->B * (d->ldt / DK) && !d->g_mul && d->x_div == 1 && d->arith == SEP_ARITH_F16X3 &&
                           (!d->g_split || (d->g_split % BM == 0 && d->g_split < d->M)) && d->x_mode >= 0 && d->x_mode <= SEP_PRO_GLN_PRELU;
     bool ptrs_ok = plain_ok;
     for (int k = 0; k < n && ptrs_ok; ++k)

@@ -1,10 +1,47 @@
 // Device helpers shared by the GEMM translation units (gemm.hip, gemm_coop.hip) of libsepkernels: float4 access, DPP row
-// sums, the LDS-transposed float4 epilogue, LDS-DMA issue / wait helpers and the two-part fp16 split.  gfx950 only.
+// sums, the LDS-transposed float4 epilogue, LDS-DMA issue / wait helpers and the two-part fp16 split; and the host dispatchers' shared
+// tables (which fused instances exist, which prologues, what the producer / consumer weight-gradient kernels take).  gfx950 only.
 #pragma once
 #include "common.hpp"
 #include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// ======================================================================================
+// The dispatch tables of the 1x1 contractions, written once.
+//
+// The fused products of the Conv-TasNet step that exist as compile-time instances: one row per combination,
+//     (trans_a, prologue, two-source contraction, epilogue flags, SEPK_COOP_MI4 bit)
+// trans_a is the orientation in which the step uses the combination: the direct kernel (gemm.hip) matches it, the packed
+// kernels (gemm_pc.hip, gemm_coop.hip) never look at it.  The SEPK_COOP_MI4 bit selects the combination's 512-row
+// cooperative form (0: it has none).  PK rows exist in all three families, DIRECT rows in the direct kernel alone (the packed
+// dispatchers hand SEP_COMBO_SKIP for them).  A row applies when the descriptor equals it in all four fields, so the rows
+// exclude each other and their order means nothing.  The launch macros stringize a row's arguments for sep_last_kernel():
+// they must do so themselves -- SEP_PRO_* / SEP_EPI_* are #defines, and an argument handed on to a second macro arrives there
+// as a number.
+#define SEP_FUSED_COMBOS(PK, DIRECT)                                                                                                              \
+    PK(false, SEP_PRO_NONE, false, SEP_EPI_STATS_PRELU, 1)                          /* TCN conv1 */                                               \
+    PK(false, SEP_PRO_GLN_PRELU, false, SEP_EPI_RESIDUAL, 0)                        /* heads */                                                   \
+    PK(false, SEP_PRO_GLN_PRELU, false, 0, 0)                                       /* last layer: skip head only */                              \
+    PK(false, SEP_PRO_PRELU, false, SEP_EPI_SIGMOID, 0)                             /* mask (sigmoid) */                                          \
+    PK(false, SEP_PRO_PRELU, false, 0, 0)                                           /* mask without its activation (softmax over channels, staged layers) */ \
+    PK(false, SEP_PRO_GLN, false, 0, 0)                                             /* bottleneck */                                              \
+    PK(false, SEP_PRO_NONE, false, 0, 4)                                            /* plain 1x1 conv (packed: input gradient too) */             \
+    DIRECT(false, SEP_PRO_NONE, false, SEP_EPI_RESIDUAL, 0)                         /* heads of the staged (causal) layers: input already normalised */ \
+    PK(true, SEP_PRO_NONE, true, 0, 2)                                              /* heads^T where its gLN sums come from the weight gradient; heads^T of the staged layers */ \
+    DIRECT(true, SEP_PRO_NONE, false, 0, 0)                                         /* plain input gradient */                                    \
+    PK(true, SEP_PRO_NONE, false, SEP_EPI_PRELU_BWD, 0)                             /* mask^T */                                                  \
+    PK(true, SEP_PRO_NONE, true, SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU, 0)        /* heads^T */                                                 \
+    PK(true, SEP_PRO_NONE, false, SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU, 0)       /* last layer's skip^T */                                     \
+    PK(true, SEP_PRO_NONE, false, SEP_EPI_ROWSUMS, 0)                               /* bottleneck^T */                                            \
+    PK(true, SEP_PRO_GLN_BWD, false, SEP_EPI_RESIDUAL, 0)                           /* conv1^T */                                                 \
+    PK(true, SEP_PRO_GLN_BWD, false, 0, 0)
+#define SEP_COMBO_SKIP(T, P, S, E, MI4)
+// The prologues of sep_pw_gemm, (prologue, has a two-source form): the direct kernel's run-time-flag instances (direct_rt) are
+// these x both orientations x the two-source forms.
+#define SEP_GEMM_PROLOGUES(X) X(SEP_PRO_NONE, 1) X(SEP_PRO_PRELU, 1) X(SEP_PRO_GLN, 1) X(SEP_PRO_GLN_PRELU, 1) X(SEP_PRO_GLN_BWD, 0)
+// The prologues of sep_pw_wgrad (sep_wgrad_desc.x_mode): every weight-gradient family but the plain fallback has one instance each.
+#define SEP_WGRAD_XMODES(X) X(SEP_PRO_NONE) X(SEP_PRO_PRELU) X(SEP_PRO_GLN) X(SEP_PRO_GLN_PRELU)
 
 namespace {
 
@@ -298,6 +335,14 @@ struct GrpOps { float4 ext[GRP], aux[GRP], old[GRP]; float bs[GRP], rs[GRP]; };
 // ======================================================================================
 constexpr int DK = 16;      // contraction rows per ring stage
 constexpr int NST = 4;      // ring depth of the weight-gradient kernel
+
+// Host side: what the two producer / consumer weight-gradient kernels (wgrad_pc.hip, wgrad_pc16.hip) ask of a descriptor alike.  Each
+// family adds its own tile shapes, arithmetic and SEPK_WGRAD_* switch.  max_b: samples whose gLN constants fit the kernel's LDS table.
+inline bool wgrad_pc_takes(const sep_wgrad_desc* d, const int max_b) {
+    if (d->g_mul || d->x_div != 1 || d->B > max_b || d->g_split % 128 != 0) return false;
+    if ((size_t)d->M * d->ldt * 4 >= (1ull << 32) || (size_t)d->N * d->ldt * 4 >= (1ull << 32)) return false;      // 32-bit DMA offsets
+    return (long)d->nsplit <= (long)d->B * (d->ldt / DK);
+}
 
 // s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier as BUILTINS: the compiler's waitcnt pass then knows every counter is zero
 // here and emits counted lgkmcnt(N) waits afterwards (behind an opaque asm it falls back to lgkmcnt(0) everywhere)

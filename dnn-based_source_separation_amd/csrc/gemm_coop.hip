@@ -457,7 +457,7 @@ void launch_coop(const sep_gemm_desc& d, const int ns, hipStream_t stream, const
     const int NR = d.M / (128 * MI);
     const int NC = d.B * (d.ldt / CBN);
     const int grid = 8 * NR * ceil_div(NC, 8);
-    sep_set_kernel(ns == 3 ? name_ns3 : name_ns2);                             // sep_last_kernel(): spelled by SEP_LC / SEP_LC4 from the arguments they instantiate
+    sep_set_kernel(ns == 3 ? name_ns3 : name_ns2);                             // sep_last_kernel(): spelled by SEP_LC from the arguments it instantiates
     if (ns == 3) hipLaunchKernelGGL((pw_gemm_coop_kernel<MI, PRO, SPLIT, EF, 3>), dim3(grid), dim3(256), 0, stream, d);
     else hipLaunchKernelGGL((pw_gemm_coop_kernel<MI, PRO, SPLIT, EF, 2>), dim3(grid), dim3(256), 0, stream, d);
 }
@@ -500,36 +500,17 @@ int sep_pw_gemm_packed(const sep_gemm_desc* d, hipStream_t stream) {
     // (means of three alternating runs on one box).
     static const int mi4 = force_mi == 4 ? 7 : getenv("SEPK_COOP_MI4") ? atoi(getenv("SEPK_COOP_MI4")) : SEP_COOP_MI4_DEFAULT;
 #define SEP_CN(MI, TAIL) "coop<" MI "," TAIL ",ns=2>", "coop<" MI "," TAIL ",ns=3>"
-#define SEP_LC4(P, S, E)                                                                    \
-    do {                                                                                    \
-        launch_coop<4, P, S, E>(*d, ns, stream, SEP_CN("4", #P "," #S "," #E));             \
-        return 1;                                                                           \
-    } while (0)
-    if ((mi4 & 1) && force_mi != 1 && force_mi != 2 && d->M % 512 == 0 && !sp && pm == SEP_PRO_NONE && ef == SEP_EPI_STATS_PRELU) SEP_LC4(SEP_PRO_NONE, false, SEP_EPI_STATS_PRELU);
-    if ((mi4 & 2) && force_mi != 1 && force_mi != 2 && d->M % 512 == 0 && sp && pm == SEP_PRO_NONE && ef == 0) SEP_LC4(SEP_PRO_NONE, true, 0);
-    if ((mi4 & 4) && force_mi != 1 && force_mi != 2 && d->M % 512 == 0 && !sp && pm == SEP_PRO_NONE && ef == 0) SEP_LC4(SEP_PRO_NONE, false, 0);
-#undef SEP_LC4
-#define SEP_LC(P, S, E)                                                                                 \
-    do {                                                                                                \
-        if (mi == 2) launch_coop<2, P, S, E>(*d, ns, stream, SEP_CN("2", #P "," #S "," #E));            \
-        else launch_coop<1, P, S, E>(*d, ns, stream, SEP_CN("1", #P "," #S "," #E));                    \
-        return 1;                                                                                       \
-    } while (0)
-    // the (prologue, two-source contraction, epilogue) combinations of the Conv-TasNet step, epilogue flags compile-time
-    if (!sp && pm == SEP_PRO_NONE && ef == SEP_EPI_STATS_PRELU) SEP_LC(SEP_PRO_NONE, false, SEP_EPI_STATS_PRELU);                      // TCN conv1
-    if (!sp && pm == SEP_PRO_GLN_PRELU && ef == SEP_EPI_RESIDUAL) SEP_LC(SEP_PRO_GLN_PRELU, false, SEP_EPI_RESIDUAL);                 // heads
-    if (!sp && pm == SEP_PRO_GLN_PRELU && ef == 0) SEP_LC(SEP_PRO_GLN_PRELU, false, 0);                                               // last layer: skip head only
-    if (!sp && pm == SEP_PRO_PRELU && ef == SEP_EPI_SIGMOID) SEP_LC(SEP_PRO_PRELU, false, SEP_EPI_SIGMOID);                           // mask (sigmoid)
-    if (!sp && pm == SEP_PRO_PRELU && ef == 0) SEP_LC(SEP_PRO_PRELU, false, 0);                                                       // mask (softmax follows)
-    if (!sp && pm == SEP_PRO_GLN && ef == 0) SEP_LC(SEP_PRO_GLN, false, 0);                                                           // bottleneck
-    if (!sp && pm == SEP_PRO_NONE && ef == 0) SEP_LC(SEP_PRO_NONE, false, 0);                                                         // plain 1x1 conv / input gradient
-    if (!sp && pm == SEP_PRO_NONE && ef == SEP_EPI_PRELU_BWD) SEP_LC(SEP_PRO_NONE, false, SEP_EPI_PRELU_BWD);                         // mask^T
-    if (sp && pm == SEP_PRO_NONE && ef == 0) SEP_LC(SEP_PRO_NONE, true, 0);                                                           // heads^T (its gLN sums come from the weight gradient)
-    if (sp && pm == SEP_PRO_NONE && ef == (SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU)) SEP_LC(SEP_PRO_NONE, true, SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU);    // heads^T
-    if (!sp && pm == SEP_PRO_NONE && ef == (SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU)) SEP_LC(SEP_PRO_NONE, false, SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU);  // last layer's skip^T
-    if (!sp && pm == SEP_PRO_NONE && ef == SEP_EPI_ROWSUMS) SEP_LC(SEP_PRO_NONE, false, SEP_EPI_ROWSUMS);                             // bottleneck^T
-    if (!sp && pm == SEP_PRO_GLN_BWD && ef == SEP_EPI_RESIDUAL) SEP_LC(SEP_PRO_GLN_BWD, false, SEP_EPI_RESIDUAL);                     // conv1^T
-    if (!sp && pm == SEP_PRO_GLN_BWD && ef == 0) SEP_LC(SEP_PRO_GLN_BWD, false, 0);
+    const bool mi4_ok = force_mi != 1 && force_mi != 2 && d->M % 512 == 0;
+    // One row of the fused products (gemm_common.hpp), epilogue flags compile-time.  A row without a SEPK_COOP_MI4 bit has no 512-row form:
+    // its first test is constant false and the branch names the MI = 2 instance, so that no MI = 4 kernel is instantiated for it.
+#define SEP_LC(T, P, S, E, MI4)                                                                                        \
+    if (sp == S && pm == P && ef == (E)) {                                                                             \
+        if (mi4_ok && (mi4 & (MI4))) launch_coop<(MI4) ? 4 : 2, P, S, E>(*d, ns, stream, SEP_CN("4", #P "," #S "," #E)); \
+        else if (mi == 2) launch_coop<2, P, S, E>(*d, ns, stream, SEP_CN("2", #P "," #S "," #E));                      \
+        else launch_coop<1, P, S, E>(*d, ns, stream, SEP_CN("1", #P "," #S "," #E));                                   \
+        return 1;                                                                                                      \
+    }
+    SEP_FUSED_COMBOS(SEP_LC, SEP_COMBO_SKIP)
 #undef SEP_LC
 #undef SEP_CN
     return 0;

@@ -344,11 +344,6 @@ __global__ __launch_bounds__(512, 2) void pw_gemm_pc_kernel(const sep_gemm_desc 
                             w[e] = x;
                         }
                     }
-#ifdef PCD_PROBE_NOSPLIT      // ceiling probe (tools/call_r08o.sh): X as if it arrived pre-split -- WRONG results, timing only
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { hi[cc][q] = __builtin_bit_cast(unsigned, w[2 * q]); lo[cc][q] = __builtin_bit_cast(unsigned, w[2 * q + 1]); }
-                    continue;
-#endif
                     float m = fmaxf(fmaxf(fmaxf(fmaxf(fabsf(w[0]), fabsf(w[1])), fabsf(w[2])), fmaxf(fmaxf(fabsf(w[3]), fabsf(w[4])), fabsf(w[5]))),
                                     fmaxf(fabsf(w[6]), fabsf(w[7])));
                     // the column's other 8 contraction rows sit in the neighbouring lane (quad_perm [1,0,3,2])
@@ -601,26 +596,13 @@ int sep_pw_gemm_pc(const sep_gemm_desc* d, hipStream_t stream) {
     const int ef = d->epi_flags, pm = d->pro_mode;
     const bool sp = d->k_split != 0;
     const bool tall = d->M % 256 == 0 && !force_22;      // 256 x 128 tile (consumers 4 x 1), else 128 x 256 (2 x 2)
-#define SEP_LP(P, S, E)                                                                          \
-    do {                                                                                         \
+#define SEP_LP(T, P, S, E, MI4)                                                                  \
+    if (sp == S && pm == P && ef == (E)) {                                                       \
         if (tall) launch_pcd<4, 1, P, S, E>(*d, stream, "pc<4,1," #P "," #S "," #E ">");         \
         else launch_pcd<2, 2, P, S, E>(*d, stream, "pc<2,2," #P "," #S "," #E ">");              \
         return 1;                                                                                \
-    } while (0)
-    if (!sp && pm == SEP_PRO_NONE && ef == SEP_EPI_STATS_PRELU) SEP_LP(SEP_PRO_NONE, false, SEP_EPI_STATS_PRELU);                      // TCN conv1
-    if (!sp && pm == SEP_PRO_GLN_PRELU && ef == SEP_EPI_RESIDUAL) SEP_LP(SEP_PRO_GLN_PRELU, false, SEP_EPI_RESIDUAL);                 // heads
-    if (!sp && pm == SEP_PRO_GLN_PRELU && ef == 0) SEP_LP(SEP_PRO_GLN_PRELU, false, 0);                                               // last layer: skip head only
-    if (!sp && pm == SEP_PRO_PRELU && ef == SEP_EPI_SIGMOID) SEP_LP(SEP_PRO_PRELU, false, SEP_EPI_SIGMOID);                           // mask (sigmoid)
-    if (!sp && pm == SEP_PRO_PRELU && ef == 0) SEP_LP(SEP_PRO_PRELU, false, 0);                                                       // mask (softmax follows)
-    if (!sp && pm == SEP_PRO_GLN && ef == 0) SEP_LP(SEP_PRO_GLN, false, 0);                                                           // bottleneck
-    if (!sp && pm == SEP_PRO_NONE && ef == 0) SEP_LP(SEP_PRO_NONE, false, 0);                                                         // plain 1x1 conv / input gradient
-    if (!sp && pm == SEP_PRO_NONE && ef == SEP_EPI_PRELU_BWD) SEP_LP(SEP_PRO_NONE, false, SEP_EPI_PRELU_BWD);                         // mask^T
-    if (sp && pm == SEP_PRO_NONE && ef == 0) SEP_LP(SEP_PRO_NONE, true, 0);                                                           // heads^T (its gLN sums come from the weight gradient)
-    if (sp && pm == SEP_PRO_NONE && ef == (SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU)) SEP_LP(SEP_PRO_NONE, true, SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU);    // heads^T
-    if (!sp && pm == SEP_PRO_NONE && ef == (SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU)) SEP_LP(SEP_PRO_NONE, false, SEP_EPI_ROWSUMS | SEP_EPI_ROWSUMS_PRELU);  // last layer's skip^T
-    if (!sp && pm == SEP_PRO_NONE && ef == SEP_EPI_ROWSUMS) SEP_LP(SEP_PRO_NONE, false, SEP_EPI_ROWSUMS);                             // bottleneck^T
-    if (!sp && pm == SEP_PRO_GLN_BWD && ef == SEP_EPI_RESIDUAL) SEP_LP(SEP_PRO_GLN_BWD, false, SEP_EPI_RESIDUAL);                     // conv1^T
-    if (!sp && pm == SEP_PRO_GLN_BWD && ef == 0) SEP_LP(SEP_PRO_GLN_BWD, false, 0);
+    }
+    SEP_FUSED_COMBOS(SEP_LP, SEP_COMBO_SKIP)      // gemm_common.hpp: the fused products, one row each
 #undef SEP_LP
     return 0;
 }

@@ -443,24 +443,15 @@ void launch_wpc(const sep_wgrad_desc& d, hipStream_t stream, const char* name) {
 // Called by sep_pw_wgrad (gemm.hip) for the split arithmetics.  Returns 1 when the call was launched here.
 int sep_pw_wgrad_pc(const sep_wgrad_desc* d, hipStream_t stream) {
     static const bool off = getenv("SEPK_WGRAD_PC") != nullptr && atoi(getenv("SEPK_WGRAD_PC")) == 0;
-    if (off || d->g_mul || d->x_div != 1 || d->B > WPMAXB || d->g_split % 128 != 0) return 0;
     const bool tall = d->M % 256 == 0 && d->N % 128 == 0;
     const bool wide = d->M % 128 == 0 && d->N % 256 == 0;
-    if (!tall && !wide) return 0;
-    if ((size_t)d->M * d->ldt * 4 >= (1ull << 32) || (size_t)d->N * d->ldt * 4 >= (1ull << 32)) return 0;      // 32-bit DMA offsets
-    if ((long)d->nsplit > (long)d->B * (d->ldt / DK)) return 0;
-#define SEP_LW(XM)                                           \
-    do {                                                     \
+    if (off || (!tall && !wide) || !wgrad_pc_takes(d, WPMAXB)) return 0;
+#define SEP_LW(XM)                                                           \
+    case XM:                                                                 \
         if (tall) launch_wpc<4, 1, XM>(*d, stream, "wgrad_pc<4,1," #XM ">"); \
         else launch_wpc<2, 2, XM>(*d, stream, "wgrad_pc<2,2," #XM ">");      \
-        return 1;                                            \
-    } while (0)
-    switch (d->x_mode) {
-        case SEP_PRO_NONE: SEP_LW(SEP_PRO_NONE);
-        case SEP_PRO_PRELU: SEP_LW(SEP_PRO_PRELU);
-        case SEP_PRO_GLN: SEP_LW(SEP_PRO_GLN);
-        default: SEP_LW(SEP_PRO_GLN_PRELU);
-    }
+        return 1;
+    switch (d->x_mode) { SEP_WGRAD_XMODES(SEP_LW) }
 #undef SEP_LW
     return 0;
 }

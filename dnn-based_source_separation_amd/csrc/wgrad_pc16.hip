@@ -58,24 +58,17 @@ __device__ __forceinline__ int w16_f8(const int row) { return ((row >> 1) & 1) |
 __device__ __forceinline__ f32x16 w16_mfma(const u32x4_t a, const u32x4_t b, const f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
 }
-// W16_CEILING_PROBE (tools/call_r08n.sh only): the main loop WITHOUT its workgroup barriers -- wrong results, no hang (nothing spins): the time such
-// a build takes bounds what a flag protocol instead of the barrier per chunk could gain
-#ifdef W16_CEILING_PROBE
-#define W16_BARRIER() do { } while (0)
-#else
-#define W16_BARRIER() __builtin_amdgcn_s_barrier()
-#endif
 template <int N>
 __device__ __forceinline__ void w16_wait_barrier() {      // vmcnt(N) lgkmcnt(0), then the workgroup barrier
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));
-    W16_BARRIER();
+    __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
 __device__ __forceinline__ void w16_lgkm0_barrier() {
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_waitcnt(0xc07f);
-    W16_BARRIER();
+    __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
 // Single-instruction forms (see gemm_pc.hip): the maximum with the lane 32 away as one v_permlane32_swap (no LDS round trip in the middle
@@ -389,12 +382,6 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
         auto split_exp = [&](auto mic, const bool live) __attribute__((always_inline)) {
             constexpr int mi = decltype(mic)::value;
             if constexpr (G2PRE && mi == 1) { (void)live; gdelta[mi] = 0; W16_SB(); return; }      // one scale per row and sample, fixed by sep_split_rows
-#if defined(W16_PROBE_NOSPLIT) || defined(W16_PROBE_NOSPLIT_MI1)      // ceiling probes (tools/call_r08o.sh, r08r): G (or the second row block of every wave) as if it arrived pre-split -- WRONG results, timing only
-#ifdef W16_PROBE_NOSPLIT_MI1
-            if (mi == 1)
-#endif
-            { (void)live; gdelta[mi] = 0; W16_SB(); return; }
-#endif
             const float rsum = ((ra[mi][0] + ra[mi][1]) + (ra[mi][2] + ra[mi][3])) + ((ra[mi][4] + ra[mi][5]) + (ra[mi][6] + ra[mi][7]));
             bias_acc[mi] += (do_bias && live) ? rsum : 0.f;
             float m = w16_amax8(ra[mi]);
@@ -415,14 +402,7 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
                 W16_SB();
                 return;
             }
-#if defined(W16_PROBE_NOSPLIT)
-            hi = __builtin_bit_cast(unsigned, ra[mi][2 * q]); lo = __builtin_bit_cast(unsigned, ra[mi][2 * q + 1]);
-#elif defined(W16_PROBE_NOSPLIT_MI1)
-            if (mi == 1) { hi = __builtin_bit_cast(unsigned, ra[mi][2 * q]); lo = __builtin_bit_cast(unsigned, ra[mi][2 * q + 1]); }
-            else w16_split2_pair(__builtin_ldexpf(ra[mi][2 * q], gexp[mi]), __builtin_ldexpf(ra[mi][2 * q + 1], gexp[mi]), hi, lo);
-#else
             w16_split2_pair(__builtin_ldexpf(ra[mi][2 * q], gexp[mi]), __builtin_ldexpf(ra[mi][2 * q + 1], gexp[mi]), hi, lo);
-#endif
             sa[par][mi][0][q] = hi;
             sa[par][mi][1][q] = lo;
             asm volatile("" : "+v"(sa[par][mi][0]), "+v"(sa[par][mi][1]));
@@ -650,17 +630,19 @@ void launch_w16_batch(const W16Batch& b, int n, hipStream_t stream, const char* 
     hipLaunchKernelGGL((pw_wgrad_pc16_batch_kernel<WR, WC, XMODE>), dim3(n * b.per), dim3(512), 0, stream, b);
 }
 
+// The descriptors this family takes, single or batched: the rule it shares with wgrad_pc.hip, its arithmetic, its switch and its tile.
+// 256 x 128 workgroup tiles only: with three operand buffers the 128 x 256 form does not fit the LDS; such shapes (one launch of the
+// Conv-TasNet step: the bottleneck's 128 x 512) go to the exact bf16 kernel (wgrad_pc.hip)
+bool w16_accepts(const sep_wgrad_desc* d) {
+    static const bool off = getenv("SEPK_WGRAD_F16") != nullptr && atoi(getenv("SEPK_WGRAD_F16")) == 0;
+    return !off && d->arith == SEP_ARITH_F16X3 && d->M % 256 == 0 && d->N % 128 == 0 && wgrad_pc_takes(d, W16MAXB);
+}
+
 }  // namespace
 
 // Called by sep_pw_wgrad (gemm.hip) for SEP_ARITH_F16X3.  Returns 1 when the call was launched here (same shapes as sep_pw_wgrad_pc).
 int sep_pw_wgrad_pc16(const sep_wgrad_desc* d, hipStream_t stream) {
-    static const bool off = getenv("SEPK_WGRAD_F16") != nullptr && atoi(getenv("SEPK_WGRAD_F16")) == 0;
-    if (off || d->arith != SEP_ARITH_F16X3 || d->g_mul || d->x_div != 1 || d->B > W16MAXB || d->g_split % 128 != 0) return 0;
-    // 256 x 128 workgroup tiles only: with three operand buffers the 128 x 256 form does not fit the LDS; such shapes (one launch of the
-    // Conv-TasNet step: the bottleneck's 128 x 512) go to the exact bf16 kernel (wgrad_pc.hip)
-    if (d->M % 256 != 0 || d->N % 128 != 0) return 0;
-    if ((size_t)d->M * d->ldt * 4 >= (1ull << 32) || (size_t)d->N * d->ldt * 4 >= (1ull << 32)) return 0;      // 32-bit DMA offsets
-    if ((long)d->nsplit > (long)d->B * (d->ldt / DK)) return 0;
+    if (!w16_accepts(d)) return 0;
     // second G source handed over PRE-SPLIT (sep_split_rows): the heads' [dout; dS] with dS split once per step for all layers.  One 256-row tile
     // (M = 256, g_split = 128), slabs inside one sample (the row scales are per sample), the bias partials of those rows come with it.
     if (d->G2_pre != nullptr) {
@@ -676,34 +658,16 @@ int sep_pw_wgrad_pc16(const sep_wgrad_desc* d, hipStream_t stream) {
         else launch_w16<4, 1, SEP_PRO_NONE, true>(q, stream, "wgrad_pc16_pre<4,1,SEP_PRO_NONE>");
         return 1;
     }
-#define SEP_LW(XM)                                           \
-    do {                                                     \
-        launch_w16<4, 1, XM>(*d, stream, "wgrad_pc16<4,1," #XM ">"); \
-        return 1;                                            \
-    } while (0)
-    switch (d->x_mode) {
-        case SEP_PRO_NONE: SEP_LW(SEP_PRO_NONE);
-        case SEP_PRO_PRELU: SEP_LW(SEP_PRO_PRELU);
-        case SEP_PRO_GLN: SEP_LW(SEP_PRO_GLN);
-        default: SEP_LW(SEP_PRO_GLN_PRELU);
-    }
+#define SEP_LW(XM) case XM: launch_w16<4, 1, XM>(*d, stream, "wgrad_pc16<4,1," #XM ">"); return 1;
+    switch (d->x_mode) { SEP_WGRAD_XMODES(SEP_LW) }
 #undef SEP_LW
     return 0;
-}
-
-static bool w16_takes(const sep_wgrad_desc* d) {
-    static const bool off = getenv("SEPK_WGRAD_F16") != nullptr && atoi(getenv("SEPK_WGRAD_F16")) == 0;
-    if (off || d->arith != SEP_ARITH_F16X3 || d->g_mul || d->x_div != 1 || d->B > W16MAXB || d->g_split % 128 != 0) return false;
-    if (d->M % 256 != 0 || d->N % 128 != 0) return false;
-    if ((size_t)d->M * d->ldt * 4 >= (1ull << 32) || (size_t)d->N * d->ldt * 4 >= (1ull << 32)) return false;
-    if ((long)d->nsplit > (long)d->B * (d->ldt / DK)) return false;
-    return true;
 }
 
 // Called by sep_pw_wgrad_batch (gemm.hip): n products whose descriptors differ in G, G2, X, partial, partial_bias only (the caller has checked
 // that).  Returns 1 when they were launched here as ONE grid.
 int sep_pw_wgrad_pc16_batch(const sep_wgrad_desc* ds, int n, hipStream_t stream) {
-    if (n < 1 || n > W16_MAXBATCH || !w16_takes(&ds[0])) return 0;
+    if (n < 1 || n > W16_MAXBATCH || !w16_accepts(&ds[0])) return 0;
     W16Batch b;
     b.d = ds[0];
     const int ntiles = (ds[0].M / 256) * (ds[0].N / 128);
@@ -712,11 +676,8 @@ int sep_pw_wgrad_pc16_batch(const sep_wgrad_desc* ds, int n, hipStream_t stream)
         const sep_wgrad_desc& q = ds[k < n ? k : 0];
         b.G[k] = q.G; b.G2[k] = q.G2; b.X[k] = q.X; b.partial[k] = q.partial; b.partial_bias[k] = q.partial_bias;
     }
-    switch (ds[0].x_mode) {
-        case SEP_PRO_NONE: launch_w16_batch<4, 1, SEP_PRO_NONE>(b, n, stream, "wgrad_pc16_batch<4,1,SEP_PRO_NONE>"); break;
-        case SEP_PRO_PRELU: launch_w16_batch<4, 1, SEP_PRO_PRELU>(b, n, stream, "wgrad_pc16_batch<4,1,SEP_PRO_PRELU>"); break;
-        case SEP_PRO_GLN: launch_w16_batch<4, 1, SEP_PRO_GLN>(b, n, stream, "wgrad_pc16_batch<4,1,SEP_PRO_GLN>"); break;
-        default: launch_w16_batch<4, 1, SEP_PRO_GLN_PRELU>(b, n, stream, "wgrad_pc16_batch<4,1,SEP_PRO_GLN_PRELU>"); break;
-    }
-    return 1;
+#define SEP_LW(XM) case XM: launch_w16_batch<4, 1, XM>(b, n, stream, "wgrad_pc16_batch<4,1," #XM ">"); return 1;
+    switch (ds[0].x_mode) { SEP_WGRAD_XMODES(SEP_LW) }
+#undef SEP_LW
+    return 0;
 }

@@ -66,11 +66,12 @@ EPI_NAME = {0: "0", STATS: "SEP_EPI_STATS_PRELU", RES: "SEP_EPI_RESIDUAL", SIG: 
 BOOL = {0: "false", 1: "true", False: "false", True: "true"}
 SLOTS = 16
 
-# (prologue, two-source, epilogue) of the packed-weight kernels: the SEP_LP lines of gemm_pc.hip and the SEP_LC lines of gemm_coop.hip
+# (prologue, two-source, epilogue) of the packed-weight kernels (gemm_pc.hip, gemm_coop.hip): the PK rows of SEP_FUSED_COMBOS in
+# csrc/gemm_common.hpp, restated by hand -- this file is what the device is compared against and is not generated from that table
 PACKED_COMBOS = [(NONE, 0, STATS), (GLN_PRELU, 0, RES), (GLN_PRELU, 0, 0), (PRELU, 0, SIG), (PRELU, 0, 0), (GLN, 0, 0), (NONE, 0, 0), (NONE, 0, PBWD),
                  (NONE, 1, 0), (NONE, 1, ROWSP), (NONE, 0, ROWSP), (NONE, 0, ROWS), (GLN_BWD, 0, RES), (GLN_BWD, 0, 0)]
 COOP_MI4 = [(NONE, 0, STATS), (NONE, 1, 0), (NONE, 0, 0)]          # bits 0, 1, 2 of SEPK_COOP_MI4 (default 2)
-# (trans_a, prologue, two-source, epilogue) of the direct kernel's compile-time instances: the SEP_LD lines of gemm.hip
+# (trans_a, prologue, two-source, epilogue) of the direct kernel's compile-time instances: all rows of that table, PK and DIRECT
 DIRECT_COMBOS = [(0, NONE, 0, STATS), (0, GLN_PRELU, 0, RES), (0, GLN_PRELU, 0, 0), (0, PRELU, 0, SIG), (0, PRELU, 0, 0), (0, GLN, 0, 0), (0, NONE, 0, 0),
                  (0, NONE, 0, RES), (1, NONE, 1, 0), (1, NONE, 0, 0), (1, NONE, 0, PBWD), (1, NONE, 1, ROWSP), (1, NONE, 0, ROWSP), (1, NONE, 0, ROWS),
                  (1, GLN_BWD, 0, RES), (1, GLN_BWD, 0, 0)]

@@ -54,14 +54,29 @@ def test_the_union_over_the_environments_is_the_ledger(reached):
 
 
 def test_the_ledger_lists_every_launch_line_of_the_dispatchers():
-    """INSTANCES against the sources: one SEP_LP / SEP_LC / SEP_LC4 / SEP_LD line or SEP_LAUNCH_DIRECT case per combination"""
+    """INSTANCES against the sources: the dispatchers' one table of fused products (SEP_FUSED_COMBOS, csrc/gemm_common.hpp: a PK row exists in
+    the packed families and the direct kernel, a DIRECT row in the direct kernel alone) and one list of prologues (SEP_GEMM_PROLOGUES:
+    direct_rt), each row restated by hand in tests/gemm_matrix.py; every dispatcher expands the table once and spells no combination itself"""
+    import re
     csrc = os.path.join(ROOT, "dnn-based_source_separation_amd", "csrc")
-    count = lambda f, *calls: sum(open(os.path.join(csrc, f)).read().count(c) for c in calls)
-    assert count("gemm_pc.hip", "SEP_LP(SEP_PRO_") == len(GM.PACKED_COMBOS) == 14
-    assert count("gemm_coop.hip", "SEP_LC(SEP_PRO_") == 14 and count("gemm_coop.hip", "SEP_LC4(SEP_PRO_") == len(GM.COOP_MI4) == 3
-    assert count("gemm.hip", "SEP_LD(false, SEP_PRO_", "SEP_LD(true, SEP_PRO_") == len(GM.DIRECT_COMBOS) == 16
-    assert 2 * count("gemm.hip", "SEP_LAUNCH_DIRECT(false, SEP_PRO_", "SEP_LAUNCH_DIRECT(true, SEP_PRO_") + \
-        count("gemm.hip", "SEP_LG(false, SEP_PRO_", "SEP_LG(true, SEP_PRO_") == len(GM.DIRECT_RT_ALL) == 18
+    text = lambda f: open(os.path.join(csrc, f)).read()
+    val = {"false": 0, "true": 1, "0": 0, **{v: k for k, v in GM.PRO_NAME.items()}, **{v: k for k, v in GM.EPI_NAME.items()}}
+    rows = [(kind, val[t], val[p], val[s], val[e], int(bit)) for kind, t, p, s, e, bit in
+            re.findall(r"^ +(PK|DIRECT)\((false|true), (SEP_PRO_\w+), (false|true), ([^,]+), (\d)\)", text("gemm_common.hpp"), re.M)]
+    packed = [r for r in rows if r[0] == "PK"]
+    assert len(packed) == len(GM.PACKED_COMBOS) == 14 and set(r[2:5] for r in packed) == set(GM.PACKED_COMBOS)
+    assert set(r[2:5] for r in packed if r[1]) == GM.BACKWARD                      # the orientation the step uses each packed combination in
+    mi4 = sorted((r[5], r[2:5]) for r in rows if r[5])
+    assert len(mi4) == len(GM.COOP_MI4) == 3 and mi4 == [(1 << i, c) for i, c in enumerate(GM.COOP_MI4)] and all(r[0] == "PK" for r in rows if r[5])
+    assert len(rows) == len(GM.DIRECT_COMBOS) == 16 and set(r[1:5] for r in rows) == set(GM.DIRECT_COMBOS)
+    pros = re.search(r"^#define SEP_GEMM_PROLOGUES\(X\)(.*)$", text("gemm_common.hpp"), re.M).group(1)
+    pros = [(val[p], int(two)) for p, two in re.findall(r"X\((SEP_PRO_\w+), ([01])\)", pros)]
+    rt = [GM.direct_rt_name(tr, p, sp) for p, two in pros for tr in (0, 1) for sp in range(1 + two)]
+    assert len(rt) == len(GM.DIRECT_RT_ALL) == 18 and sorted(rt) == sorted(GM.DIRECT_RT_ALL)
+    for f in ("gemm_pc.hip", "gemm_coop.hip", "gemm.hip"):
+        assert text(f).count("SEP_FUSED_COMBOS(") == 1, f
+        assert not re.search(r"\(\s*(?:(?:false|true)\s*,\s*)?SEP_PRO_\w+\s*,\s*(?:false|true)\s*,", text(f)), f      # (prologue, two-source, ... spelled out
+    assert text("gemm.hip").count("SEP_GEMM_PROLOGUES(") == 1
     assert len(GM.INSTANCES) == 28 + 2 * (28 + 3) + (14 * 3 + 2) + 18 + 1
 
 
