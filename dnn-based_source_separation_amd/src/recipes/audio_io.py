@@ -1,10 +1,11 @@
 """
-Minimal wav reader / writer on the standard library (`wave`) + numpy, and an installable stand-in for the three
+Minimal wav reader / writer on the standard library (`wave`) + numpy, and an installable stand-in for the
 `torchaudio` calls the reference recipes make (`torchaudio.load(path, frame_offset=, num_frames=)`,
-`torchaudio.save(path, tensor, sample_rate=, bits_per_sample=)`, `torchaudio.info`): the image has no torchaudio
- and the wsj0-mix data are plain PCM wav files.
+`torchaudio.save(path, tensor, sample_rate=, bits_per_sample=)`, `torchaudio.info`, and the rate conversion
+`torchaudio.transforms.Resample` / `torchaudio.functional.resample` on sepkernels/resample.py): the image has no
+torchaudio and the wsj0-mix data are plain PCM wav files.
 
-reference call sites: egs/wsj0-mix/common/src/dataset.py:37,81,89 and driver.py:195,202.
+reference call sites: egs/wsj0-mix/common/src/dataset.py:37,81,89, driver.py:195,202 and egs/musdb18/common/src/dataset.py:623.
 """
 import sys
 import types
@@ -65,7 +66,8 @@ def write_wav(path, signal, sample_rate, bits_per_sample=16):
 
 
 def install_torchaudio_shim():
-    """Registers a `torchaudio` module exposing load / save / info on top of this file (no-op if the real one imports)."""
+    """Registers a `torchaudio` module exposing load / save / info on top of this file and transforms.Resample / functional.resample on
+    sepkernels/resample.py (no-op if the real one imports)."""
     try:
         import torchaudio  # noqa: F401
         return False
@@ -81,6 +83,12 @@ def install_torchaudio_shim():
             self.bits_per_sample = 8 * sw
 
     shim.info = _Info
+    from sepkernels import resample as _resample
+    shim.transforms = types.ModuleType("torchaudio.transforms")
+    shim.transforms.Resample = _resample.Resample
+    shim.functional = types.ModuleType("torchaudio.functional")
+    shim.functional.resample = _resample.resample
+    sys.modules["torchaudio.transforms"], sys.modules["torchaudio.functional"] = shim.transforms, shim.functional
     shim.__version__ = "0.0+sepkernels.shim"
     sys.modules["torchaudio"] = shim
     return True

@@ -255,6 +255,9 @@ SIGNATURES = {
     "sep_stitch_cost": [_vp, _vp] + [_I] * 5 + [_vp],
     "sep_stitch_chain": [_vp, _vp] + [_I] * 3 + [_vp],
     "sep_stitch_ola": [_vp] * 3 + [_I] * 6 + [_vp],
+    # sample-rate conversion (ABI 23, additive): rows of whole signals, rows of an online call with a history per stream
+    "sep_resample_fwd": [_vp, _L, _vp, _vp, _vp, _L, _I, _L, _L] + [_I] * 4 + [_vp],
+    "sep_resample_stream_fwd": [_vp] * 6 + [_I] * 7 + [_vp],
 }
 _RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_last_kernel": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
              "sep_gln_tokens_ws_bytes": ctypes.c_size_t, "sep_online_state_row_bytes": ctypes.c_size_t, "sep_bss_scratch_bytes": ctypes.c_size_t,
@@ -433,7 +436,7 @@ def _check(rc, name):
 
 def last_kernel():
     """Name of the kernel instance this thread's last pw_gemm / pw_wgrad / pw_wgrad_batch launch, or its last call of a streaming dispatcher
-    (encoder_fwd, dwconv_fwd / _bwd, decoder_fwd / _bwd, depthwise_*, split_rows, gln_tokens_*, cln_*, depthwise_cln_*), went to
+    (encoder_fwd, dwconv_fwd / _bwd, decoder_fwd / _bwd, depthwise_*, split_rows, gln_tokens_*, cln_*, depthwise_cln_*, resample_*), went to
     (sep_last_kernel: family and template arguments, e.g. 'pc<4,1,SEP_PRO_GLN_PRELU,false,SEP_EPI_RESIDUAL>', 'dwconv_bwd_row<3,8,true>',
     'decoder_bwd<16,2>/nz1'), '' before the first one.  Not a launch: never recorded."""
     return load().sep_last_kernel().decode()
@@ -974,6 +977,16 @@ class HipBackend:
 
     def stitch_ola(self, est, perm_abs, out, B, W, n, win, hop, T):
         _check(load().sep_stitch_ola(_ptr(est, _f32), _ptr(perm_abs, torch.int64), _ptr(out, _f32), B, W, n, win, hop, T, _stream()), "sep_stitch_ola")
+
+    # ... sample-rate conversion (sepkernels/resample.py): table (Kc, u) fp32 tap-major, first (u,) int32; x holds R rows of T samples at
+    # pitch x_pitch, y R rows of T_out at pitch y_pitch; chunk (A, m o), history (num_streams, H), slots (A,) int32 or None
+    def resample_fwd(self, x, x_pitch, table, first, y, y_pitch, R, T, T_out, o, u, width, Kc):
+        _check(load().sep_resample_fwd(_ptr(x, _f32), x_pitch, _ptr(table, _f32), _ptr(first, torch.int32), _ptr(y, _f32), y_pitch, R, T, T_out, o, u, width,
+                                       Kc, _stream()), "sep_resample_fwd")
+
+    def resample_stream_fwd(self, chunk, table, first, history, y, slots, A, num_streams, m, o, u, width, Kc):
+        _check(load().sep_resample_stream_fwd(_ptr(chunk, _f32), _ptr(table, _f32), _ptr(first, torch.int32), _ptr(history, _f32), _ptr(y, _f32),
+                                              _ptr(slots, torch.int32), A, num_streams, m, o, u, width, Kc, _stream()), "sep_resample_stream_fwd")
 
 
 _backend = HipBackend()

@@ -892,6 +892,48 @@ int sep_stitch_cost(const float* est, double* cost, int B, int W, int n, int win
 int sep_stitch_chain(const int64_t* perm_local, int64_t* perm_abs, int B, int W, int n, sep_stream_t stream);
 int sep_stitch_ola(const float* est, const int64_t* perm_abs, float* out, int B, int W, int n, int win, int hop, int T, sep_stream_t stream);
 
+/* ---- Sample-rate conversion: whole signals and online streams (ABI 23, additive; csrc/resample.hip, sepkernels/resample.py) ----------------------
+ * The definition is torchaudio.functional.resample, restated here in full because that package is on none of our machines.  With
+ * g = gcd(orig_freq, new_freq), o = orig_freq / g, u = new_freq / g, lpw = lowpass_filter_width (6) and rolloff (0.99):
+ *     base  = min(o, u) rolloff,   width = ceil(lpw o / base),   K = 2 width + o
+ *     t[p][k] = clamp(((k - width) / o - p / u) base, -lpw, lpw)                          p in [0, u), k in [0, K)
+ *     h[p][k] = sinc(pi t) w(t) base / o,   sinc(0) = 1,   w(t) = cos(pi t / (2 lpw))^2                       ("sinc_interp_hann")
+ *                                           or             w(t) = i0(beta sqrt(1 - (t / lpw)^2)) / i0(beta)   ("sinc_interp_kaiser", beta 14.769656459379492)
+ *     y[i u + p] = sum_k h[p][k] x[i o + k - width],   x = 0 outside [0, T),   T_out = ceil(u T / o)
+ * everything formed in fp64 and then cast.  The table is the CALLER's (sepkernels/resample.py builds it on the host), and it is handed over
+ * COMPACT: of every phase the Kc taps from first[p] on, table[j u + p] = (float)h[p][first[p] + j], j < Kc (tap-major: consecutive phases are
+ * consecutive words), 0 <= first[p] <= K - Kc, so that every tap left out is negligible (the module drops leading and trailing taps below
+ * 2^-60 of the phase's largest; Kc is the longest run that leaves, 67 of K = 509 at 44.1 k -> 8 k).  table and first (u int32) are device memory;
+ * the library cannot look at them: an entry of first outside [0, K - Kc] is read as the nearest end of that range, nothing is indexed out of range.
+ *   sep_resample_fwd         x: R rows of T fp32 samples at pitch x_pitch >= T; y: R rows of T_out at pitch y_pitch >= T_out (pitches in elements).
+ *                            y[r][i u + p] = sum_{j < Kc} table[j u + p] x[r][i o + first[p] + j - width], added by fmaf in ascending j from +0
+ *                            in fp32 -- the same sequence for every output of a phase wherever it lies in the row.  Nothing outside [0, T) of a
+ *                            row is read (the zeros are a predicate), elements [T_out, y_pitch) are not written, every element below T_out is
+ *                            written once by the thread that owns it: no atomics, two runs give the same bits.  A workgroup stages the input
+ *                            span of a tile of frames in LDS beside the table.  Instances (sep_last_kernel): "resample_frames<U>" for
+ *                            u = U <= 3 (a thread per frame, the tap of a step wave-uniform) and "resample_phases" for any u (a thread per
+ *                            output, lanes on consecutive phases).  All offsets are 64-bit.
+ *   sep_resample_stream_fwd  A rows of an online call.  chunk (A, m o), y (A, m u), history (num_streams, H) with D = ceil(width / o) o and
+ *                            H = width + D.  Row j belongs to stream slots[j] (device memory of A distinct entries in [0, num_streams), the
+ *                            convention of sep_online_*_sel: read when the kernel runs, not checked; NULL means row j is stream j and
+ *                            A = num_streams); rows of history that slots does not name are neither read nor written.  With
+ *                            cat = [history of the slot | row j of chunk]: y[j][i u + p] = sum_{j' < Kc} table[j' u + p] cat[i o + first[p] + j'],
+ *                            the arithmetic of sep_resample_fwd, tap for tap -- so a stream that starts from a zero history computes
+ *                            sep_resample_fwd of [D zeros | its samples] bit for bit however it is cut into chunks, frame by frame as the samples
+ *                            arrive (delay: D input samples), and m = D / o frames of zero samples flush the rest.  The history then becomes the
+ *                            last H samples of cat, also when the chunk is shorter than H.  RACE-FREE BY OWNERSHIP, no second buffer: one
+ *                            workgroup per (row, tile of frames); the history row is read and written by the workgroup of the row's tile 0
+ *                            alone, which reads its input span and the H samples of the new history before a barrier and writes after it; a
+ *                            geometry in which a later tile would reach back into the history is refused.  Instances "resample_stream_frames<U>",
+ *                            "resample_stream_phases".
+ * Refused with a message before any launch: a null pointer, T_out != ceil(u T / o), a pitch shorter than its row, Kc > K, K > 8192 (the staged
+ * span), u > 1024, Kc u > 6144 (the table's LDS), H > SEP_RESAMPLE_MAX_HISTORY, more than 2^31 - 1 tiles.  The module then takes its composed route. */
+#define SEP_RESAMPLE_MAX_HISTORY 2048
+int sep_resample_fwd(const float* x, int64_t x_pitch, const float* table, const int32_t* first, float* y, int64_t y_pitch, int R, int64_t T,
+                     int64_t T_out, int o, int u, int width, int Kc, sep_stream_t stream);
+int sep_resample_stream_fwd(const float* chunk, const float* table, const int32_t* first, float* history, float* y, const int32_t* slots, int A,
+                            int num_streams, int m, int o, int u, int width, int Kc, sep_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
