@@ -15,9 +15,6 @@
 
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
 constexpr int CLN_TCOLS = 64;        // frames per column-sum block (one lane each), 4 waves share the channels
 
 // ws[b][0][t], ws[b][1][t] <- the two column sums of frame t

@@ -70,6 +70,10 @@ __device__ __forceinline__ T block_sum_n(T v, T* sm) {
     return r;
 }
 
+// 16-byte access to four consecutive floats (p 16-byte aligned)
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+
 __device__ __forceinline__ float prelu_f(float x, float a) { return x > 0.f ? x : a * x; }
 __device__ __forceinline__ float prelu_grad(float x, float a) { return x > 0.f ? 1.f : a; }
 

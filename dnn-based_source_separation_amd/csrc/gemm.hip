@@ -89,12 +89,8 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_kernel(const sep_gemm_desc d) 
     const int NR = (d.M + BM - 1) / BM;
     const int ntile_t = d.ldt / BN;
     const int NC = d.B * ntile_t;
-    // XCD-aware decode: all row tiles of one column tile land on the same XCD (blockIdx % 8)
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, j = bid >> 3;
-    const int rt = j % NR;
-    const int ct = (j / NR) * 8 + xcd;
-    if (ct >= NC) return;
+    int rt, ct;                                     // row tile, (sample, column tile): all row tiles of one column tile on the same XCD
+    if (!xcd_decode(blockIdx.x, NR, NC, rt, ct)) return;
     const int b = ct / ntile_t;
     const int t0 = (ct % ntile_t) * BN;
     const int m0 = rt * BM;
@@ -316,17 +312,8 @@ struct __attribute__((aligned(16))) DirectSmem {
 //      32 cycles per 16-deep chunk and tile pair instead of 8 of 64.  Error per product <= 2^-23 relative, i.e. the
 //      rounding of an fp32 multiply; measured against fp64 it is no worse than the fp32 MFMA path (tests).  The
 //      lane half lk already owns k = 8*lk .. 8*lk+7 of a chunk, which is the operand layout of the bf16 instruction.
+//      (split3_pair and mfma_bf16: gemm_common.hpp)
 
-// two fp32 values -> their (hi, mid, lo) bf16 parts packed {x0 low half, x1 high half}: 11 VALU instructions
-__device__ __forceinline__ void split3_pair(const float x0, const float x1, unsigned& hi, unsigned& mid, unsigned& lo) {
-    const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
-    hi = __builtin_amdgcn_perm(u1, u0, 0x07060302u);
-    const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
-    const unsigned v0 = __float_as_uint(r0), v1 = __float_as_uint(r1);
-    mid = __builtin_amdgcn_perm(v1, v0, 0x07060302u);
-    const float q0 = r0 - __uint_as_float(v0 & 0xffff0000u), q1 = r1 - __uint_as_float(v1 & 0xffff0000u);
-    lo = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
-}
 // the 8 chunk values of one 32-row (32-column) block -> three packed operands
 __device__ __forceinline__ void split3_frag(const float (&lo4)[4], const float (&hi4)[4], u32x4_t (&out)[3]) {
     unsigned p[3][4];
@@ -336,9 +323,6 @@ __device__ __forceinline__ void split3_frag(const float (&lo4)[4], const float (
     split3_pair(hi4[2], hi4[3], p[0][3], p[1][3], p[2][3]);
 #pragma unroll
     for (int q = 0; q < 3; ++q) out[q] = u32x4_t{p[q][0], p[q][1], p[q][2], p[q][3]};
-}
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4_t a, const u32x4_t b, const f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
 }
 // acc += A * B on the split operands (6 of the 9 part products)
 __device__ __forceinline__ void mfma_split6(const u32x4_t (&a)[3], const u32x4_t (&b)[3], f32x16& acc) {
@@ -367,12 +351,9 @@ __global__ __launch_bounds__(256, (AR >= 1 ? 3 : PRO == SEP_PRO_GLN_BWD ? 3 : PR
     const int NR = (d.M + BM - 1) / BM;
     const int ntile_t = d.ldt / BN;
     const int NC = d.B * ntile_t;
-    // XCD-aware decode: all row tiles of one column tile land on the same XCD (blockIdx % 8) and share X through its L2
     const int bid = blockIdx.x;
-    const int xcd = bid & 7, j = bid >> 3;
-    const int rt = j % NR;
-    const int ct = (j / NR) * 8 + xcd;
-    if (ct >= NC) return;
+    int rt, ct;                                     // row tile, (sample, column tile): all row tiles of one column tile share X through one XCD's L2
+    if (!xcd_decode(bid, NR, NC, rt, ct)) return;
     const int b = ct / ntile_t;
     const int t0 = (ct % ntile_t) * BN;
     const int m0 = rt * BM;
@@ -829,16 +810,13 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(const sep_wgrad_desc d
     const int wr = wid >> 1, wc = wid & 1;
     const int ntm = (d.M + BM - 1) / BM, ntn = (d.N + BN - 1) / BN;
     const int ntiles = ntm * ntn;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, j = bid >> 3;
-    const int tile = j % ntiles;
-    const int s = (j / ntiles) * 8 + xcd;
-    if (s >= d.nsplit) return;
+    int tile, s;                                  // output tile, slab: all tiles of one slab on the same XCD
+    if (!xcd_decode(blockIdx.x, ntiles, d.nsplit, tile, s)) return;
     const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
 
     const int cps_t = d.ldt / WK;                 // chunks per sample
     const long chunks_total = (long)d.B * cps_t;
-    const long cper = (chunks_total + d.nsplit - 1) / d.nsplit;
+    const long cper = slab_cper(chunks_total, d.nsplit, false);      // (not slab_chunks: the loops below run on c_end, and through it this kernel's generated code changes)
     const long c_begin = (long)s * cper;
     long c_end = c_begin + cper;
     if (c_end > chunks_total) c_end = chunks_total;
@@ -1018,6 +996,7 @@ __global__ __launch_bounds__(512, 4) void pw_wgrad_direct_kernel(const sep_wgrad
     const int lk = lane >> 5, l31 = lane & 31;
     const int ntm = (d.M + BM - 1) / BM, ntn = (d.N + BN - 1) / BN;
     const int ntiles = ntm * ntn;
+    // the rule of xcd_decode (gemm_common.hpp: tile = inner, s = outer) spelled out: through the helper this kernel's generated code changes
     const int bid = blockIdx.x;
     const int xcd = bid & 7, j = bid >> 3;
     const int tile = j % ntiles;
@@ -1026,12 +1005,8 @@ __global__ __launch_bounds__(512, 4) void pw_wgrad_direct_kernel(const sep_wgrad
     const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
 
     const int cps_t = d.ldt / DK;                  // chunks per sample
-    const long chunks_total = (long)d.B * cps_t;
-    const long cper = (chunks_total + d.nsplit - 1) / d.nsplit;
-    const long c_begin = (long)s * cper;
-    long c_end = c_begin + cper;
-    if (c_end > chunks_total) c_end = chunks_total;
-    const int nk_all = (int)(c_end > c_begin ? c_end - c_begin : 0);
+    long c_begin;
+    const int nk_all = slab_chunks((long)d.B * cps_t, d.nsplit, false, s, c_begin);
     const int nk_max = (nk_all + 1) >> 1;          // trips of the shared loop (group 0's chunk count)
     const int nk = (nk_all + 1 - grp) >> 1;        // chunks of THIS group: c_begin + grp, +2, ...
 
@@ -1278,6 +1253,7 @@ __global__ __launch_bounds__(256, 3) void pw_wgrad_split_kernel(const sep_wgrad_
     const int lk = lane >> 5, l31 = lane & 31;
     const int ntm = (d.M + BM - 1) / BM, ntn = (d.N + BN - 1) / BN;
     const int ntiles = ntm * ntn;
+    // the rule of xcd_decode (gemm_common.hpp: tile = inner, s = outer) spelled out: through the helper this kernel's generated code changes
     const int bid = blockIdx.x;
     const int xcd = bid & 7, j = bid >> 3;
     const int tile = j % ntiles;
@@ -1286,12 +1262,8 @@ __global__ __launch_bounds__(256, 3) void pw_wgrad_split_kernel(const sep_wgrad_
     const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
 
     const int cps_t = d.ldt / DK;                  // chunks per sample
-    const long chunks_total = (long)d.B * cps_t;
-    const long cper = (chunks_total + d.nsplit - 1) / d.nsplit;
-    const long c_begin = (long)s * cper;
-    long c_end = c_begin + cper;
-    if (c_end > chunks_total) c_end = chunks_total;
-    const int nk = (int)(c_end > c_begin ? c_end - c_begin : 0);
+    long c_begin;
+    const int nk = slab_chunks((long)d.B * cps_t, d.nsplit, false, s, c_begin);
 
     const float alpha_x = X_PRELU ? d.x_alpha[0] : 0.f;
     if (X_GLN) {
@@ -1607,7 +1579,7 @@ extern "C" int sep_pw_gemm(const sep_gemm_desc* d, sep_stream_t stream) {
     }
     const int NR = ceil_div(d->M, BM);
     const int NC = d->B * (d->ldt / BN);
-    const int grid = 8 * NR * ceil_div(NC, 8);
+    const int grid = xcd_grid(NR, NC);
     // fast path: direct-to-LDS high-occupancy kernel; the register-staged kernel remains for shapes outside its limits
     static const bool force_staged = getenv("SEPK_FORCE_STAGED") != nullptr;
     const bool direct_ok = !force_staged && d->K % DK == 0 && d->k_split % DK == 0 && d->M >= 4 && d->M % 4 == 0 &&
@@ -1684,7 +1656,7 @@ extern "C" int sep_pw_wgrad(const sep_wgrad_desc* d, sep_stream_t stream) {
     if (d->x_mode == SEP_PRO_PRELU || d->x_mode == SEP_PRO_GLN_PRELU) SEP_REQUIRE(d->x_alpha, "sep_pw_wgrad: needs x_alpha");
     if (d->x_mode >= SEP_PRO_GLN) SEP_REQUIRE(d->x_stats && d->x_gamma && d->x_beta && d->count > 0, "sep_pw_wgrad: gLN prologue needs stats/gamma/beta/count");
     const int ntiles = ceil_div(d->M, BM) * ceil_div(d->N, BN);
-    const int grid = 8 * ntiles * ceil_div(d->nsplit, 8);
+    const int grid = xcd_grid(ntiles, d->nsplit);
     static const bool force_staged = getenv("SEPK_FORCE_STAGED") != nullptr;
     const bool direct_ok = !force_staged && !d->g_mul && (d->x_mode < SEP_PRO_GLN || d->B / d->x_div <= WMAXB) &&
                            (long)d->nsplit <= (long)d->B * (d->ldt / DK);

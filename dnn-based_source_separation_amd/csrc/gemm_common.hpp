@@ -1,6 +1,9 @@
-// Device helpers shared by the GEMM translation units (gemm.hip, gemm_coop.hip) of libsepkernels: float4 access, DPP row
-// sums, the LDS-transposed float4 epilogue, LDS-DMA issue / wait helpers and the two-part fp16 split; and the host dispatchers' shared
-// tables (which fused instances exist, which prologues, what the producer / consumer weight-gradient kernels take).  gfx950 only.
+// What the five 1x1-contraction translation units of libsepkernels (gemm.hip, gemm_coop.hip, gemm_pc.hip, wgrad_pc.hip, wgrad_pc16.hip)
+// share, each piece written once.  Device side: DPP row sums, the LDS-transposed float4 epilogue, LDS-DMA issue / wait / barrier helpers,
+// the two partition rules of the grids (XCD-aware block decode, slabs of the weight gradients) and the arithmetic contract of
+// SEP_ARITH_F16X3 / SEP_ARITH_BF16X6: the MFMA wrappers, the two-part fp16 and three-part bf16 splits, the running scale exponent and the
+// single-instruction wave primitives that go with them.  Host side: the dispatchers' tables (which fused instances exist, which
+// prologues, what the producer / consumer weight-gradient kernels take) and the grid sizes that match the decode.  gfx950 only.
 #pragma once
 #include "common.hpp"
 #include <type_traits>
@@ -45,8 +48,46 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a compile-time constant in the body
+template <int N, int I = 0, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<N, I + 1>(f); }
+}
+
+// ======================================================================================
+// The two partition rules of the grids, device and host side.
+//
+// XCD-aware block decode: the hardware deals consecutive workgroups round-robin to the eight XCDs (blockIdx % 8), so the workgroups that
+// share an operand -- all row tiles of one column tile of a product (they share X), all tiles of one slab of a weight gradient -- are
+// given block indices that land on the SAME XCD and meet in its L2.  `inner` counts those sharers (0 .. n_inner - 1), `outer` what they
+// share; false: the block lies in the padding of the grid (n_outer rounded up to whole groups of eight) and has nothing to do.
+// xcd_grid is the grid that goes with it.
+// ======================================================================================
+__device__ __forceinline__ bool xcd_decode(const int bid, const int n_inner, const int n_outer, int& inner, int& outer) {
+    const int xcd = bid & 7, j = bid >> 3;
+    inner = j % n_inner;
+    outer = (j / n_inner) * 8 + xcd;
+    return outer < n_outer;
+}
+inline int xcd_grid(const int n_inner, const int n_outer) { return 8 * n_inner * ceil_div(n_outer, 8); }
+
+// Slabs of the weight gradients: the (sample, frame) columns of the contraction, counted in chunks (chunks_total = B * chunks per
+// sample), are dealt to nsplit slabs of slab_cper chunks each; the last slabs may be short or empty.  pairs: whole chunk PAIRS per slab
+// (the fp16 family fetches two 16-frame chunks per 128-byte line, so its slab boundaries sit on 32-frame marks; ldt % 32 == 0).
+// slab_chunks: slab s is the chunks [c_begin, c_begin + nk), nk returned (even with `pairs`).
+__host__ __device__ __forceinline__ long slab_cper(const long chunks_total, const int nsplit, const bool pairs) {
+    long cper = (chunks_total + nsplit - 1) / nsplit;
+    if (pairs) cper += cper & 1;
+    return cper;
+}
+__device__ __forceinline__ int slab_chunks(const long chunks_total, const int nsplit, const bool pairs, const int s, long& c_begin) {
+    const long cper = slab_cper(chunks_total, nsplit, pairs);
+    c_begin = (long)s * cper;
+    long c_end = c_begin + cper;
+    if (c_end > chunks_total) c_end = chunks_total;
+    return (int)(c_end > c_begin ? c_end - c_begin : 0);
+}
+
 __device__ __forceinline__ const float* byte_off(const float* base, unsigned bytes) {
     return reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (size_t)bytes);
 }
@@ -370,6 +411,21 @@ __device__ __forceinline__ void wait_all_and_barrier() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
+// vmcnt(N) lgkmcnt(0), then the workgroup barrier: all but this wave's newest N DMA instructions have landed, its LDS accesses are done
+template <int N>
+__device__ __forceinline__ void wait_vm_barrier() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+// lgkmcnt(0) alone, then the barrier: for the waves that have no DMA of their own to wait for (vmcnt left as it is)
+__device__ __forceinline__ void lgkm0_barrier() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
 // LDS-DMA of 16 B per lane as an asm statement, saddr form: source = base (SGPR pair) + zext(voff), LDS image lane-linear
 // from the wave-uniform byte address lds_dst.  Why not the builtin: hipcc books a global_load_lds as a FLAT access that may
 // touch LDS, and from then on every LDS-read dependency in the loop becomes s_waitcnt lgkmcnt(0) -- no counted waits, so
@@ -420,11 +476,24 @@ typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4_t;
 // tools/gemm_accuracy.py and the kernel tests put it at the fp32-MFMA path's level on operands spread over e^+-6.
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
+// Two forms of the same split, hi = fp16(x) toward zero, lo = fp16(x - hi), packed {x0 low half, x1 high half}.  This one is plain C++
+// and is what the direct kernel (gemm.hip) and the weight packer (gemm_coop.hip) use; split2_pair_mix below forms lo = x - float(hi half)
+// as ONE mixed-precision FMA per value (exact: the fp16 operand is extended, the arithmetic is fp32), an instruction hipcc does not pick
+// by itself, for the producer waves and splitters whose instruction COUNT is what their main loop waits for.  Same bits; they stay two
+// functions because folding one into the other changes the generated code of its callers.
 __device__ __forceinline__ void split2_pair(const float x0, const float x1, unsigned& hi, unsigned& lo) {
     const fp16x2_t h = __builtin_amdgcn_cvt_pkrtz(x0, x1);
     const fp16x2_t l = __builtin_amdgcn_cvt_pkrtz(x0 - (float)h.x, x1 - (float)h.y);
     hi = __builtin_bit_cast(unsigned, h);
     lo = __builtin_bit_cast(unsigned, l);
+}
+__device__ __forceinline__ void split2_pair_mix(const float x0, const float x1, unsigned& hi, unsigned& lo) {
+    const fp16x2_t h = __builtin_amdgcn_cvt_pkrtz(x0, x1);
+    hi = __builtin_bit_cast(unsigned, h);
+    float l0, l1;
+    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(l0) : "v"(x0), "v"(hi));
+    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(l1) : "v"(x1), "v"(hi));
+    lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(l0, l1));
 }
 __device__ __forceinline__ void split2_frag(const float (&lo4)[4], const float (&hi4)[4], u32x4_t (&out)[2]) {
     unsigned p[2][4];
@@ -435,10 +504,54 @@ __device__ __forceinline__ void split2_frag(const float (&lo4)[4], const float (
 #pragma unroll
     for (int q = 0; q < 2; ++q) out[q] = u32x4_t{p[q][0], p[q][1], p[q][2], p[q][3]};
 }
+// one 32x32x16 block product on packed operands (8 fp16 / bf16 values per lane and operand)
+__device__ __forceinline__ f32x16 mfma_f16(const u32x4_t a, const u32x4_t b, const f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma_bf16(const u32x4_t a, const u32x4_t b, const f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+}
+// acc += A * B on the two-part operands: hi*lo + lo*hi + hi*hi (the dropped lo*lo is <= 2^-22 |xy|)
 __device__ __forceinline__ void mfma_split3(const u32x4_t (&a)[2], const u32x4_t (&b)[2], f32x16& acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[0]), __builtin_bit_cast(f16x8_t, b[1]), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[1]), __builtin_bit_cast(f16x8_t, b[0]), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a[0]), __builtin_bit_cast(f16x8_t, b[0]), acc, 0, 0, 0);
+    acc = mfma_f16(a[0], b[1], acc);
+    acc = mfma_f16(a[1], b[0], acc);
+    acc = mfma_f16(a[0], b[0], acc);
+}
+// The running scale exponent of the scaled operands: a column of X (a row of an activation in the weight gradients) is multiplied by
+// 2^cur before it is split.  Given the maximum m of its next 16 values: unchanged while the scaled maximum stays below 2^14 (fp16
+// overflows at 2^16), else re-centred so that this maximum lands in [2^8, 2^9); a chunk of zeros never moves it.  Branch-free.
+// F16X3_UNSET is the exponent of a column that has only seen zeros: any first maximum "outgrows" it, and ldexp(0, anything) stays 0.
+constexpr int F16X3_UNSET = 10000;
+__device__ __forceinline__ int f16x3_next_exp(const float m, const int cur) {
+    const int ex = __builtin_amdgcn_frexp_expf(m);                       // m = f 2^ex, f in [0.5, 1)
+    const int ex2 = __builtin_bit_cast(int, m) == 0 ? -3 * F16X3_UNSET : ex;
+    return ex2 + cur > 14 ? 9 - ex : cur;
+}
+// Single-instruction forms the compiler does not produce by itself (a producer wave is issue-bound: gemm_pc.hip): v_max_f32 without the
+// canonicalising v_max(x, x) in front, and the maximum with the neighbouring lane as ONE dpp instruction (the s_nop covers the
+// VALU-write -> DPP-read hazard the compiler cannot see behind asm).
+__device__ __forceinline__ float vmax_raw(const float a, const float b) {
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float max_lane_xor1(const float m) {      // max(m, m of lane ^ 1)
+    float r;
+    asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=&v"(r) : "v"(m));
+    return r;
+}
+
+// SEP_ARITH_BF16X6: fp32 products from the EXACT three-way bf16 split of both operands, x = hi + mid + lo with each part a truncated
+// bf16 (8 + 8 + 8 significand bits), six of the nine part products on v_mfma_f32_32x32x16_bf16 (gemm.hip, wgrad_pc.hip).
+// two fp32 values -> their (hi, mid, lo) parts packed {x0 low half, x1 high half}; hi + mid + lo == x exactly: 11 VALU instructions
+__device__ __forceinline__ void split3_pair(const float x0, const float x1, unsigned& hi, unsigned& mid, unsigned& lo) {
+    const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
+    hi = __builtin_amdgcn_perm(u1, u0, 0x07060302u);
+    const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
+    const unsigned v0 = __float_as_uint(r0), v1 = __float_as_uint(r1);
+    mid = __builtin_amdgcn_perm(v1, v0, 0x07060302u);
+    const float q0 = r0 - __uint_as_float(v0 & 0xffff0000u), q1 = r1 - __uint_as_float(v1 & 0xffff0000u);
+    lo = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
 }
 
 }  // namespace

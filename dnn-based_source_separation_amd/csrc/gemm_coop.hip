@@ -65,46 +65,18 @@ constexpr int coop_occupancy() {
     return by_lds < by_regs ? by_lds : by_regs;
 }
 
-// single-instruction forms hipcc does not emit by itself (see gemm_pc.hip): v_max_f32 without the canonicalising v_max(x, x), the quad
-// maximum as two dpp instructions, lo = x - float(hi half) as one mixed-precision FMA
-__device__ __forceinline__ float co_vmax(const float a, const float b) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
+// the quad maximum as two dpp instructions (single-instruction forms hipcc does not emit by itself, like max_lane_xor1 of gemm_common.hpp)
 __device__ __forceinline__ float co_quad_max(const float m) {               // max over the four lanes of a quad, in every lane
     float r, t;
     asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=&v"(t) : "v"(m));
     asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "=&v"(r) : "v"(t));
     return r;
 }
-__device__ __forceinline__ void co_split2_pair(const float x0, const float x1, unsigned& hi, unsigned& lo) {
-    const fp16x2_t h = __builtin_amdgcn_cvt_pkrtz(x0, x1);
-    hi = __builtin_bit_cast(unsigned, h);
-    float l0, l1;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(l0) : "v"(x0), "v"(hi));
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(l1) : "v"(x1), "v"(hi));
-    lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(l0, l1));
-}
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void pco_unroll(F&& f) {      // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>)
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); pco_unroll<N, I + 1>(f); }
-}
-__device__ __forceinline__ f32x16 mfma_f16(const u32x4_t a, const u32x4_t b, const f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-}
 // max over the four lanes of a quad, in every lane: two VALU with DPP operands
 __device__ __forceinline__ float quad_max(float x) {
     x = fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true)));   // quad_perm [1,0,3,2]
     x = fmaxf(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true)));   // quad_perm [2,3,0,1]
     return x;
-}
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm0_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));      // vmcnt(N) lgkmcnt(0)
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
 }
 
 template <int MI, int PRO, bool SPLIT, int EF, int NS>
@@ -125,12 +97,8 @@ void pw_gemm_coop_kernel(const sep_gemm_desc d) {
     const int NR = d.M / BMc;
     const int ntile_t = d.ldt / CBN;
     const int NC = d.B * ntile_t;
-    // XCD-aware decode: all row tiles of one column tile land on the same XCD (blockIdx % 8) and share X through its L2
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, jj = bid >> 3;
-    const int rt = jj % NR;
-    const int ct = (jj / NR) * 8 + xcd;
-    if (ct >= NC) return;
+    int rt, ct;                                          // row tile, (sample, column tile): all row tiles of one column tile share X through one XCD's L2
+    if (!xcd_decode(blockIdx.x, NR, NC, rt, ct)) return;
     const int b = ct / ntile_t;
     const int t0 = (ct % ntile_t) * CBN;
     const int m0 = rt * BMc;
@@ -205,8 +173,7 @@ void pw_gemm_coop_kernel(const sep_gemm_desc d) {
     const int s_lo = col_s * 16 + 4 * ((2 * (kq >> 1) + 1) ^ s_fsw) + 2 * (kq & 1);
     const bool s_live = t0 + col_s < d.T;
     const unsigned st_lane_off = 4u * (unsigned)(4 * kq * d.ldt + col_s);   // GLN_BWD store-back: this thread's byte offset in a chunk
-    constexpr int UNSET = 10000;                                     // scale exponent of a column that has only seen zeros: any first maximum
-    int bexp = UNSET;                                                // "outgrows" it, and ldexp(0, UNSET) stays 0
+    int bexp = F16X3_UNSET;                                          // the column's running scale exponent (f16x3_next_exp)
     const bool fast_prelu = alpha_p >= 0.f && alpha_p <= 1.f;        // PReLU(x) = max(x, alpha x) there
 
     float raw[4], aux[4], v[4];
@@ -244,26 +211,24 @@ void pw_gemm_coop_kernel(const sep_gemm_desc d) {
                 }
                 x = da;
             } else {
-                if (P_PRELU) x = fast_prelu ? co_vmax(x, alpha_p * x) : prelu_f(x, alpha_p);
+                if (P_PRELU) x = fast_prelu ? vmax_raw(x, alpha_p * x) : prelu_f(x, alpha_p);
                 if (P_GLN) x = fmaf(x, scv[j], shv[j]);
             }
             v[j] = x;
         }
     };
-    // column scale of the chunk (the column's 16 values sit in the four lanes of a quad): branch-free, see gemm_pc.hip
+    // column scale of the chunk (the column's 16 values sit in the four lanes of a quad)
     auto scale_vals = [&]() {
         float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
         m = co_quad_max(m);
-        const int e = __builtin_amdgcn_frexp_expf(m);                    // m = f * 2^e, f in [0.5, 1)
-        const int e2 = __builtin_bit_cast(int, m) == 0 ? -3 * UNSET : e; // a chunk of zeros never moves the scale
-        bexp = e2 + bexp > 14 ? 9 - e : bexp;                            // first non-zero chunk, or the column outgrew its scale
+        bexp = f16x3_next_exp(m, bexp);                                  // moves with the first non-zero chunk, or when the column outgrew its scale
     };
     unsigned h01, l01, h23, l23;
     auto split_vals = [&]() {
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = __builtin_ldexpf(v[j], bexp);
-        co_split2_pair(v[0], v[1], h01, l01);
-        co_split2_pair(v[2], v[3], h23, l23);
+        split2_pair_mix(v[0], v[1], h01, l01);
+        split2_pair_mix(v[2], v[3], h23, l23);
     };
     auto write_vals = [&](const int pb) {
         float* Bp = sm.Bp[pb];
@@ -337,24 +302,24 @@ void pw_gemm_coop_kernel(const sep_gemm_desc d) {
         CO_SB();
         rescale();
         CO_SB();
-        pco_unroll<NM / 3>([&](auto ic) { M(CO_I(P), ic); });
+        static_for<NM / 3>([&](auto ic) { M(CO_I(P), ic); });
         if (more) pro_vals(s + 1);
         CO_SB();
-        pco_unroll<NM / 6>([&](auto ic) { M(CO_I(P), CO_I(decltype(ic)::value + NM / 3)); });
+        static_for<NM / 6>([&](auto ic) { M(CO_I(P), CO_I(decltype(ic)::value + NM / 3)); });
         if (more) scale_vals();
         CO_SB();
-        pco_unroll<NM / 6>([&](auto ic) { M(CO_I(P), CO_I(decltype(ic)::value + NM / 2)); });
+        static_for<NM / 6>([&](auto ic) { M(CO_I(P), CO_I(decltype(ic)::value + NM / 2)); });
         if (more) split_vals();
         CO_SB();
-        pco_unroll<NM / 6>([&](auto ic) { M(CO_I(P), CO_I(decltype(ic)::value + 2 * NM / 3)); });
+        static_for<NM / 6>([&](auto ic) { M(CO_I(P), CO_I(decltype(ic)::value + 2 * NM / 3)); });
         if (more) write_vals((s + 1) & 1);
         CO_SB();
-        pco_unroll<NM / 6>([&](auto ic) { M(CO_I(P), CO_I(decltype(ic)::value + 5 * NM / 6)); });
+        static_for<NM / 6>([&](auto ic) { M(CO_I(P), CO_I(decltype(ic)::value + 5 * NM / 6)); });
         if (more) {
             // raw X(s+2) has landed -- mine: all but the younger loads; everyone's: the barrier --, the operands of chunk s+1 are
             // written, and every wave is past its reads of this step's stages
-            if (KEEP > 0 && s + NS < nk) wait_vm_lgkm0_barrier<KEEP>();
-            else wait_vm_lgkm0_barrier<0>();
+            if (KEEP > 0 && s + NS < nk) wait_vm_barrier<KEEP>();
+            else wait_vm_barrier<0>();
             if (xi < nk) issue_x();                                      // X(s+NS+1) into the raw stage this step has read
         }
     };
@@ -367,13 +332,13 @@ void pw_gemm_coop_kernel(const sep_gemm_desc d) {
         for (int g = 0; g < NS - 1; ++g)
             if (xi < nk) issue_x();
         load_a(CO_I(0), 0);
-        wait_vm_lgkm0_barrier<0>();                    // X0 (and everything else) landed
+        wait_vm_barrier<0>();                    // X0 (and everything else) landed
         read_raw(0, 0);
         pro_vals(0);
         scale_vals();
         split_vals();
         write_vals(0);
-        wait_vm_lgkm0_barrier<0>();                    // operands of chunk 0 visible; raw stage 0 free
+        wait_vm_barrier<0>();                    // operands of chunk 0 visible; raw stage 0 free
         if (xi < nk) issue_x();                        // X(NS) -> raw stage 0
         int s = 0;
         for (; s + 1 < nk; s += 2) {
@@ -456,7 +421,7 @@ template <int MI, int PRO, bool SPLIT, int EF>
 void launch_coop(const sep_gemm_desc& d, const int ns, hipStream_t stream, const char* name_ns2, const char* name_ns3) {
     const int NR = d.M / (128 * MI);
     const int NC = d.B * (d.ldt / CBN);
-    const int grid = 8 * NR * ceil_div(NC, 8);
+    const int grid = xcd_grid(NR, NC);
     sep_set_kernel(ns == 3 ? name_ns3 : name_ns2);                             // sep_last_kernel(): spelled by SEP_LC from the arguments it instantiates
     if (ns == 3) hipLaunchKernelGGL((pw_gemm_coop_kernel<MI, PRO, SPLIT, EF, 3>), dim3(grid), dim3(256), 0, stream, d);
     else hipLaunchKernelGGL((pw_gemm_coop_kernel<MI, PRO, SPLIT, EF, 2>), dim3(grid), dim3(256), 0, stream, d);

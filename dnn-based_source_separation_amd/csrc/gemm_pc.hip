@@ -61,9 +61,6 @@ struct __attribute__((aligned(16))) PcdSmem {
 template <int WR, int WC, int NS, int NB, bool AUX>
 constexpr bool pcd_fits() { return sizeof(PcdSmem<WR, WC, NS, NB, AUX>) <= 160 * 1024; }
 
-__device__ __forceinline__ f32x16 pcd_mfma(const u32x4_t a, const u32x4_t b, const f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-}
 typedef int pcd_i4 __attribute__((ext_vector_type(4)));
 // smallest of four progress counters (one 16-byte LDS read, same address in every lane)
 #define PCD_LDS __attribute__((address_space(3)))
@@ -76,33 +73,7 @@ __device__ __forceinline__ void pcd_post(int* c, const int value) {
     *(volatile PCD_LDS int*)(PCD_LDS int*)c = value;
 }
 #define PCD_FENCE() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-// Single-instruction forms the compiler does not produce by itself (a producer wave is issue-bound, see the kernel):
-// v_max_f32 without the canonicalising v_max(x, x) in front, the neighbour-lane maximum as ONE dpp instruction (the s_nop
-// covers the VALU-write -> DPP-read hazard the compiler cannot see behind asm), and lo = x - float(hi half) as one
-// mixed-precision FMA (exact: the fp16 operand is extended, the arithmetic is fp32).
-__device__ __forceinline__ float pcd_vmax(const float a, const float b) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float pcd_max_quad_neighbour(const float m) {      // max(m, m of lane ^ 1)
-    float r;
-    asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=&v"(r) : "v"(m));
-    return r;
-}
-__device__ __forceinline__ void pcd_split2_pair(const float x0, const float x1, unsigned& hi, unsigned& lo) {
-    const fp16x2_t h = __builtin_amdgcn_cvt_pkrtz(x0, x1);
-    hi = __builtin_bit_cast(unsigned, h);
-    float l0, l1;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(l0) : "v"(x0), "v"(hi));
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(l1) : "v"(x1), "v"(hi));
-    lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(l0, l1));
-}
 constexpr int pcd_gcd(int a, int b) { return b == 0 ? a : pcd_gcd(b, a % b); }
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void pcd_unroll(F&& f) {      // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>)
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); pcd_unroll<N, I + 1>(f); }
-}
 
 template <int WR, int WC, int PRO, bool SPLIT, int EF, int NS, int NB>
 __global__ __launch_bounds__(512, 2) void pw_gemm_pc_kernel(const sep_gemm_desc d) {
@@ -127,12 +98,9 @@ __global__ __launch_bounds__(512, 2) void pw_gemm_pc_kernel(const sep_gemm_desc 
     const int NR = d.M / TM;
     const int ntile_t = d.ldt / TN;
     const int NC = d.B * ntile_t;
-    // XCD-aware decode: all row tiles of one column tile land on the same XCD (blockIdx % 8) and share X through its L2
     const int bid = blockIdx.x;
-    const int xcd = bid & 7, jj = bid >> 3;
-    const int rt = jj % NR;
-    const int ct = (jj / NR) * 8 + xcd;
-    if (ct >= NC) return;
+    int rt, ct;                                          // row tile, (sample, column tile): all row tiles of one column tile share X through one XCD's L2
+    if (!xcd_decode(bid, NR, NC, rt, ct)) return;
     const int b = ct / ntile_t;
     const int t0 = (ct % ntile_t) * TN;
     const int m0 = rt * TM;
@@ -217,10 +185,9 @@ __global__ __launch_bounds__(512, 2) void pw_gemm_pc_kernel(const sep_gemm_desc 
         const int s_fsw = (colb >> 2) & 3;                                       // 128 is a multiple of 16: same swizzle for both columns
         const int w_hi = colb * 16 + 4 * ((2 * kh) ^ s_fsw);
         const int w_lo = colb * 16 + 4 * ((2 * kh + 1) ^ s_fsw);
-        constexpr int UNSET = 10000;                                             // scale exponent of a column that has only seen zeros: any first maximum
-        int bexp[WC];                                                            // "outgrows" it (ex + UNSET > 14), and ldexp(0, UNSET) stays 0
+        int bexp[WC];                                                            // the columns' running scale exponents (f16x3_next_exp)
 #pragma unroll
-        for (int cc = 0; cc < WC; ++cc) bexp[cc] = UNSET;
+        for (int cc = 0; cc < WC; ++cc) bexp[cc] = F16X3_UNSET;
         const unsigned st_lane_off = 4u * (unsigned)(8 * kh * d.ldt + colb);     // GLN_BWD store-back: byte offset inside a chunk
         const bool edge = t0 + TN > d.T;                                         // only the last column tile of a sample has dead frames
         bool live[WC];
@@ -279,7 +246,7 @@ __global__ __launch_bounds__(512, 2) void pw_gemm_pc_kernel(const sep_gemm_desc 
 
         auto run = [&](auto fastc) {
             constexpr bool FAST = decltype(fastc)::value;                        // 0 <= alpha <= 1: PReLU(x) = max(x, alpha*x)
-            auto prelu = [&](const float x) { return FAST ? pcd_vmax(x, alpha_p * x) : prelu_f(x, alpha_p); };
+            auto prelu = [&](const float x) { return FAST ? vmax_raw(x, alpha_p * x) : prelu_f(x, alpha_p); };
             auto body = [&](const int j, auto uc) {
                 constexpr int u = decltype(uc)::value;
                 constexpr int cur = u & 1, nxt = cur ^ 1;
@@ -347,14 +314,12 @@ __global__ __launch_bounds__(512, 2) void pw_gemm_pc_kernel(const sep_gemm_desc 
                     float m = fmaxf(fmaxf(fmaxf(fmaxf(fabsf(w[0]), fabsf(w[1])), fabsf(w[2])), fmaxf(fmaxf(fabsf(w[3]), fabsf(w[4])), fabsf(w[5]))),
                                     fmaxf(fabsf(w[6]), fabsf(w[7])));
                     // the column's other 8 contraction rows sit in the neighbouring lane (quad_perm [1,0,3,2])
-                    m = pcd_max_quad_neighbour(m);
-                    const int ex = __builtin_amdgcn_frexp_expf(m);                   // m = f * 2^ex, f in [0.5, 1)
-                    const int ex2 = __builtin_bit_cast(int, m) == 0 ? -3 * UNSET : ex;     // a chunk of zeros never moves the scale
-                    bexp[cc] = ex2 + bexp[cc] > 14 ? 9 - ex : bexp[cc];              // first non-zero chunk, or the column outgrew its scale
+                    m = max_lane_xor1(m);
+                    bexp[cc] = f16x3_next_exp(m, bexp[cc]);                          // moves with the first non-zero chunk, or when the column outgrew its scale
 #pragma unroll
                     for (int e = 0; e < 8; ++e) w[e] = __builtin_ldexpf(w[e], bexp[cc]);
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) pcd_split2_pair(w[2 * q], w[2 * q + 1], hi[cc][q], lo[cc][q]);
+                    for (int q = 0; q < 4; ++q) split2_pair_mix(w[2 * q], w[2 * q + 1], hi[cc][q], lo[cc][q]);
                 }
                 // slot pb is free once every consumer has read chunk j - NB
                 if (j >= NB) {
@@ -377,7 +342,7 @@ __global__ __launch_bounds__(512, 2) void pw_gemm_pc_kernel(const sep_gemm_desc 
                 fr = pcd_load4(sm.freed);                                        // sampled now, looked at one chunk later
                 PCD_FENCE();
             };
-            for (int j0 = 0; j0 < nk; j0 += U) pcd_unroll<U>([&](auto uc) { if (j0 + decltype(uc)::value < nk) body(j0 + decltype(uc)::value, uc); });
+            for (int j0 = 0; j0 < nk; j0 += U) static_for<U>([&](auto uc) { if (j0 + decltype(uc)::value < nk) body(j0 + decltype(uc)::value, uc); });
         };
         if ((P_PRELU || P_BWD) && !(alpha_p >= 0.f && alpha_p <= 1.f)) run(std::false_type{});
         else run(std::true_type{});
@@ -459,7 +424,7 @@ __global__ __launch_bounds__(512, 2) void pw_gemm_pc_kernel(const sep_gemm_desc 
             constexpr int par = decltype(parc)::value, h = decltype(halfc)::value, i = decltype(ic)::value;
             constexpr int part = i >> 2, mi = (i >> 1) & 1, n = i & 1;
             constexpr int asel = part == 1 ? 1 : 0, bsel = part == 0 ? 1 : 0;
-            acc[h][mi][n] = pcd_mfma(sa[par][mi][asel], sb[h][n][bsel], acc[h][mi][n]);
+            acc[h][mi][n] = mfma_f16(sa[par][mi][asel], sb[h][n][bsel], acc[h][mi][n]);
             PCD_SB();
         };
         auto wait_ready = [&](const int need) {
@@ -534,12 +499,12 @@ __global__ __launch_bounds__(512, 2) void pw_gemm_pc_kernel(const sep_gemm_desc 
         load_a1(PCD_I(0), PCD_I(1), PCD_I(0), 0); load_a1(PCD_I(0), PCD_I(1), PCD_I(1), 0);
         PCD_COUNT(c_loop = -clock64());
         for (int j0 = 0; j0 < nk; j0 += UC)
-            pcd_unroll<UC>([&](auto uc) {
+            static_for<UC>([&](auto uc) {
                 constexpr int u = decltype(uc)::value;
                 phase_a(std::true_type{}, PCD_I((u & 1) ^ 1), j0 + u, u % NB);
                 phase_b(PCD_I(u & 1), PCD_I((u & 1) ^ 1), j0 + u, u % NB);
             });
-        pcd_unroll<12>([&](auto ic) { M(PCD_I((UC - 1) & 1), PCD_I(1), ic); });      // second half of the last chunk
+        static_for<12>([&](auto ic) { M(PCD_I((UC - 1) & 1), PCD_I(1), ic); });      // second half of the last chunk
         PCD_COUNT(c_loop += clock64());
         PCD_STAMP(0, 1, wall_clock64()); PCD_STAMP(0, 3, n_miss); PCD_STAMP(0, 4, n_spin); PCD_STAMP(0, 5, c_loop);
         // undo the column scales (the row scales of A leave in the epilogue)
@@ -580,7 +545,7 @@ void launch_pcd(const sep_gemm_desc& d, hipStream_t stream, const char* name) {
     constexpr int NB = pcd_fits<WR, WC, NS, 4, BWD>() ? 4 : 2;                  // even: the consumer's round is NB chunks
     const int NR = d.M / (64 * WR);
     const int NC = d.B * (d.ldt / (128 * WC));
-    const int grid = 8 * NR * ceil_div(NC, 8);
+    const int grid = xcd_grid(NR, NC);
     sep_set_kernel(name);                                                      // sep_last_kernel(): spelled by SEP_LP from the arguments it instantiates
     hipLaunchKernelGGL((pw_gemm_pc_kernel<WR, WC, PRO, SPLIT, EF, NS, NB>), dim3(grid), dim3(512), 0, stream, d);
 }

@@ -12,9 +12,6 @@
 
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
 // =====================================================================================
 // Encoder: w[b][n][f] = sum_{c,k} E[n][c][k] * xpad[b][c][S f + k]   (+ReLU), + gLN statistics of w
 // One block = 128 frames x all N basis rows.  Thread = (frame, n parity); the basis row is wave-uniform

@@ -46,35 +46,6 @@ struct __attribute__((aligned(16))) WpcSmem {
     float rstd[WPMAXB];
 };
 
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 wbf16x8_t;
-
-__device__ __forceinline__ f32x16 wp_mfma(const u32x4_t a, const u32x4_t b, const f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wbf16x8_t, a), __builtin_bit_cast(wbf16x8_t, b), c, 0, 0, 0);
-}
-// two fp32 values -> their (hi, mid, lo) truncated-bf16 parts packed {x0 low half, x1 high half}; hi + mid + lo == x exactly
-__device__ __forceinline__ void wp_split3_pair(const float x0, const float x1, unsigned& hi, unsigned& mid, unsigned& lo) {
-    const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
-    hi = __builtin_amdgcn_perm(u1, u0, 0x07060302u);
-    const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
-    const unsigned v0 = __float_as_uint(r0), v1 = __float_as_uint(r1);
-    mid = __builtin_amdgcn_perm(v1, v0, 0x07060302u);
-    const float q0 = r0 - __uint_as_float(v0 & 0xffff0000u), q1 = r1 - __uint_as_float(v1 & 0xffff0000u);
-    lo = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
-}
-template <int N>
-__device__ __forceinline__ void wp_wait_barrier() {      // vmcnt(N) lgkmcnt(0), then the workgroup barrier
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void wp_lgkm0_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
 template <int WR, int WC, int XMODE, int NS>
 __global__ __launch_bounds__(512, 2) void pw_wgrad_pc_kernel(const sep_wgrad_desc d) {
     constexpr bool X_GLN = XMODE == SEP_PRO_GLN || XMODE == SEP_PRO_GLN_PRELU;
@@ -95,19 +66,13 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc_kernel(const sep_wgrad_des
     const int ntm = d.M / TM, ntn = d.N / TN;
     const int ntiles = ntm * ntn;
     const int bid = blockIdx.x;
-    const int xcd = bid & 7, jj = bid >> 3;
-    const int tile = jj % ntiles;
-    const int s = (jj / ntiles) * 8 + xcd;
-    if (s >= d.nsplit) return;
+    int tile, s;                                   // output tile, slab: all tiles of one slab on the same XCD
+    if (!xcd_decode(bid, ntiles, d.nsplit, tile, s)) return;
     const int m0 = (tile / ntn) * TM, n0 = (tile % ntn) * TN;
 
     const int cps_t = d.ldt / DK;                  // chunks per sample
-    const long chunks_total = (long)d.B * cps_t;
-    const long cper = (chunks_total + d.nsplit - 1) / d.nsplit;
-    const long c_begin = (long)s * cper;
-    long c_end = c_begin + cper;
-    if (c_end > chunks_total) c_end = chunks_total;
-    const int nk = (int)(c_end > c_begin ? c_end - c_begin : 0);
+    long c_begin;
+    const int nk = slab_chunks((long)d.B * cps_t, d.nsplit, false, s, c_begin);
 
     if (X_GLN) {
         for (int bx = tid; bx < d.B; bx += 512) {
@@ -193,7 +158,7 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc_kernel(const sep_wgrad_des
         auto put8 = [&](float* planes, const int rows, const int row, const int half, const float (&v)[8]) {
             unsigned hi[4], mid[4], lo[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) wp_split3_pair(v[2 * q], v[2 * q + 1], hi[q], mid[q], lo[q]);
+            for (int q = 0; q < 4; ++q) split3_pair(v[2 * q], v[2 * q + 1], hi[q], mid[q], lo[q]);
             float* base = planes + (size_t)(3 * half) * rows * 4 + row * 4;
             *reinterpret_cast<u32x4_t*>(base) = u32x4_t{hi[0], hi[1], hi[2], hi[3]};
             *reinterpret_cast<u32x4_t*>(base + rows * 4) = u32x4_t{mid[0], mid[1], mid[2], mid[3]};
@@ -204,8 +169,8 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc_kernel(const sep_wgrad_des
 #pragma unroll
         for (int g = 0; g < NS; ++g)
             if (ci < nk) issue();
-        if (nk >= NS) wp_wait_barrier<(NS - 1) * G>();                           // B_-1: raw chunk 0 landed (the NS-1 newer ones may still fly)
-        else wp_wait_barrier<0>();
+        if (nk >= NS) wait_vm_barrier<(NS - 1) * G>();                           // B_-1: raw chunk 0 landed (the NS-1 newer ones may still fly)
+        else wait_vm_barrier<0>();
 
         int stage = 0;
         for (int j = 0; j < nk; ++j) {
@@ -247,16 +212,16 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc_kernel(const sep_wgrad_des
                 // (~1 us) apart, the second piece found its line evicted again -- rows of the (B, C, ldt = 4096) activations are 16 KiB apart,
                 // a few L2 sets for a tile's 384 rows: measured 1.9x the algorithmic bytes (331 MB for 173, rocprofv3 TCC_EA0_RDREQ; with a row
                 // stride of 4224 floats the same kernel read 178; profiles/r03f_wgrad_fetch.txt).
-                if (j & 1) { if (j + 3 <= nk) wp_wait_barrier<G>(); else wp_wait_barrier<0>(); }          // newer: chunk j+2
-                else { if (j + 4 <= nk) wp_wait_barrier<2 * G>(); else wp_wait_barrier<0>(); }            // newer: chunks j+2, j+3
+                if (j & 1) { if (j + 3 <= nk) wait_vm_barrier<G>(); else wait_vm_barrier<0>(); }          // newer: chunk j+2
+                else { if (j + 4 <= nk) wait_vm_barrier<2 * G>(); else wait_vm_barrier<0>(); }            // newer: chunks j+2, j+3
                 WSTAMP(1, 3);
                 if (j & 1) {
                     if (ci < nk) issue();
                     if (ci < nk) issue();
                 }
             } else {
-                if (KEEP > 0 && j + NS <= nk) wp_wait_barrier<KEEP>();
-                else wp_wait_barrier<0>();                                       // B_j
+                if (KEEP > 0 && j + NS <= nk) wait_vm_barrier<KEEP>();
+                else wait_vm_barrier<0>();                                       // B_j
                 WSTAMP(1, 3);
                 if (ci < nk) issue();                                            // chunk j+NS into the stage B_j freed
             }
@@ -297,7 +262,7 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc_kernel(const sep_wgrad_des
             if (do_bias) bias_acc[mi] += ((ra[mi][0] + ra[mi][1]) + (ra[mi][2] + ra[mi][3])) + ((ra[mi][4] + ra[mi][5]) + (ra[mi][6] + ra[mi][7]));
             unsigned hi[4], mid[4], lo[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) wp_split3_pair(ra[mi][2 * q], ra[mi][2 * q + 1], hi[q], mid[q], lo[q]);
+            for (int q = 0; q < 4; ++q) split3_pair(ra[mi][2 * q], ra[mi][2 * q + 1], hi[q], mid[q], lo[q]);
             sa[mi][0] = u32x4_t{hi[0], hi[1], hi[2], hi[3]};
             sa[mi][1] = u32x4_t{mid[0], mid[1], mid[2], mid[3]};
             sa[mi][2] = u32x4_t{lo[0], lo[1], lo[2], lo[3]};
@@ -317,7 +282,7 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc_kernel(const sep_wgrad_des
 #pragma unroll
             for (int q = 0; q < 6; ++q)
 #pragma unroll
-                for (int n = 0; n < 2; ++n) acc[h][mi][n] = wp_mfma(sa[mi][PA[q]], sb[h][n][PB[q]], acc[h][mi][n]);
+                for (int n = 0; n < 2; ++n) acc[h][mi][n] = mfma_bf16(sa[mi][PA[q]], sb[h][n][PB[q]], acc[h][mi][n]);
         };
         // One quarter (12 MFMAs) with the split of the G fragments of row block `ms` woven in: one pair of values (11 VALU) behind every
         // third MFMA, each step fenced with sched_barrier so that the VALU stay in the MFMAs' shadow.  Left to itself hipcc emits the
@@ -330,9 +295,9 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc_kernel(const sep_wgrad_des
             if (do_bias) bias_acc[ms] += ((ra[ms][0] + ra[ms][1]) + (ra[ms][2] + ra[ms][3])) + ((ra[ms][4] + ra[ms][5]) + (ra[ms][6] + ra[ms][7]));
 #pragma unroll
             for (int k = 0; k < 12; ++k) {
-                acc[h][mi][k & 1] = wp_mfma(sa[mi][PA[k >> 1]], sb[h][k & 1][PB[k >> 1]], acc[h][mi][k & 1]);
+                acc[h][mi][k & 1] = mfma_bf16(sa[mi][PA[k >> 1]], sb[h][k & 1][PB[k >> 1]], acc[h][mi][k & 1]);
                 if (k % 3 == 0) {
-                    wp_split3_pair(ra[ms][2 * (k / 3)], ra[ms][2 * (k / 3) + 1], hi[k / 3], mid[k / 3], lo[k / 3]);
+                    split3_pair(ra[ms][2 * (k / 3)], ra[ms][2 * (k / 3) + 1], hi[k / 3], mid[k / 3], lo[k / 3]);
                     asm volatile("" : "+v"(hi[k / 3]), "+v"(mid[k / 3]), "+v"(lo[k / 3]));      // materialise HERE (pure arithmetic is otherwise sunk past the MFMAs)
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -344,13 +309,13 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc_kernel(const sep_wgrad_des
         constexpr std::integral_constant<int, 0> I0{};
         constexpr std::integral_constant<int, 1> I1{};
         __syncthreads();                                                         // (the producers' table barrier)
-        wp_lgkm0_barrier();                                                      // B_-1: raw chunk 0 has landed
+        lgkm0_barrier();                                                      // B_-1: raw chunk 0 has landed
         int gstage = 0;
         if (nk > 0) read_raw_a(0);
         // chunk j after B_j: load B0 | split A0 | quarter (1,1) of chunk j-1 | split A1 | quarter (0,0) | load B1 | quarter (1,0) |
         //                    quarter (0,1) | read raw G of chunk j+1 (landed before B_j)
         if (nk > 0) {                                                            // chunk 0: nothing older to finish
-            wp_lgkm0_barrier();                                                  // B_0
+            lgkm0_barrier();                                                  // B_0
             load_b(I0, 0);
             split_a(I0);
             split_a(I1);
@@ -363,7 +328,7 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc_kernel(const sep_wgrad_des
         }
         for (int j = 1; j < nk; ++j) {
             WSTAMP(0, 0);
-            wp_lgkm0_barrier();                                                  // B_j: the X operands of chunk j are there
+            lgkm0_barrier();                                                  // B_j: the X operands of chunk j are there
             WSTAMP(0, 1);
             const int buf = j & 1;
             load_b(I0, buf);
@@ -428,7 +393,7 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc_kernel(const sep_wgrad_des
 template <int WR, int WC, int XMODE>
 void launch_wpc(const sep_wgrad_desc& d, hipStream_t stream, const char* name) {
     const int ntiles = (d.M / (64 * WR)) * (d.N / (128 * WC));
-    const int grid = 8 * ntiles * ceil_div(d.nsplit, 8);
+    const int grid = xcd_grid(ntiles, d.nsplit);
     // raw-ring depth NS (SEPK_WPC_NS = 2 | 3 | 4 for A/B runs): 4 = chunks fetched in pairs (one HBM fetch per 128-byte line), 2 / 3 = one
     // chunk per barrier, a DMA has NS - 1 chunk periods to land
     static const int ns = getenv("SEPK_WPC_NS") ? atoi(getenv("SEPK_WPC_NS")) : 4;

@@ -35,7 +35,6 @@ extern "C" int sep_debug_wpc_step(long long* out) { return hipMemcpyFromSymbol(o
 namespace {
 
 constexpr int W16MAXB = 256;      // samples whose gLN constants fit the LDS table
-constexpr int W16UNSET = 10000;   // exponent of a row that has only seen zeros: any first maximum "outgrows" it, ldexp(0, anything) = 0
 
 constexpr int W16NGP = 3, W16NXP = 2;      // raw ring depths in chunk PAIRS: G is fetched two pairs ahead of its use, X one
 constexpr int W16NXB = 3;                  // operand buffers: the producers run ONE CHUNK AHEAD of the chunk being multiplied (see the kernel)
@@ -55,24 +54,8 @@ struct __attribute__((aligned(16))) W16Smem {
 // the producers' X rows at 256 columns), and readers of 8 consecutive rows x both chunk halves (X at 128 columns: the half toggles bit 1
 // of the granule index) need bits 0 and 2 of f8 to tell i = 0..3 apart: bit 0 <- row bit 1, bit 2 <- row bit 2, bit 1 <- row bit 3.
 __device__ __forceinline__ int w16_f8(const int row) { return ((row >> 1) & 1) | (((row >> 2) & 1) << 2) | (((row >> 3) & 1) << 1); }
-__device__ __forceinline__ f32x16 w16_mfma(const u32x4_t a, const u32x4_t b, const f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void w16_wait_barrier() {      // vmcnt(N) lgkmcnt(0), then the workgroup barrier
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void w16_lgkm0_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-// Single-instruction forms (see gemm_pc.hip): the maximum with the lane 32 away as one v_permlane32_swap (no LDS round trip in the middle
-// of the MFMA stream), with the neighbouring lane as one v_max_f32_dpp, and lo = x - float(hi half) as one mixed-precision FMA.
+// The maximum with the lane 32 away as one v_permlane32_swap (no LDS round trip in the middle of the MFMA stream); with the neighbouring
+// lane it is max_lane_xor1 of gemm_common.hpp.
 __device__ __forceinline__ float w16_max_halves(const float m) {
     // v_permlane32_swap exchanges lanes 32-63 of its first operand with lanes 0-31 of its second: the operands must be two REGISTERS (the
     // builtin, handed the same value twice, was given one register by hipcc and returned garbage: tools/w16_probe.hip), hence the copy in asm
@@ -80,28 +63,8 @@ __device__ __forceinline__ float w16_max_halves(const float m) {
     asm volatile("v_mov_b32 %1, %0\n\ts_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "=&v"(b));
     return fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
 }
-__device__ __forceinline__ float w16_max_neighbour(const float m) {      // max(m, m of lane ^ 1)
-    float r;
-    asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=&v"(r) : "v"(m));
-    return r;
-}
-__device__ __forceinline__ void w16_split2_pair(const float x0, const float x1, unsigned& hi, unsigned& lo) {
-    const fp16x2_t h = __builtin_amdgcn_cvt_pkrtz(x0, x1);
-    hi = __builtin_bit_cast(unsigned, h);
-    float l0, l1;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(l0) : "v"(x0), "v"(hi));
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(l1) : "v"(x1), "v"(hi));
-    lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(l0, l1));
-}
 __device__ __forceinline__ float w16_amax8(const float (&v)[8]) {
     return fmaxf(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))), fmaxf(fmaxf(fabsf(v[4]), fabsf(v[5])), fmaxf(fabsf(v[6]), fabsf(v[7]))));
-}
-// running scale exponent of a row given the maximum of its next 16 frames: unchanged while the scaled maximum stays below 2^14 (and for a
-// chunk of zeros), else re-centred so that this maximum lands in [2^8, 2^9)
-__device__ __forceinline__ int w16_next_exp(const float m, const int cur) {
-    const int ex = __builtin_amdgcn_frexp_expf(m);                       // m = f 2^ex, f in [0.5, 1)
-    const int ex2 = __builtin_bit_cast(int, m) == 0 ? -3 * W16UNSET : ex;
-    return ex2 + cur > 14 ? 9 - ex : cur;
 }
 
 // The DMA pieces of a chunk pair (8 rows x 128 B each, 4096 B apart in LDS) in ONE statement.  Issued one by one (glds16_asm) every piece
@@ -156,20 +119,13 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
 
     const int ntm = d.M / TM, ntn = d.N / TN;
     const int ntiles = ntm * ntn;
-    const int xcd = bid & 7, jj = bid >> 3;
-    const int tile = jj % ntiles;
-    const int s = (jj / ntiles) * 8 + xcd;
-    if (s >= d.nsplit) return;
+    int tile, s;                                   // output tile, slab: all tiles of one slab on the same XCD
+    if (!xcd_decode(bid, ntiles, d.nsplit, tile, s)) return;
     const int m0 = (tile / ntn) * TM, n0 = (tile % ntn) * TN;
 
     const int cps_t = d.ldt / DK;                  // chunks per sample
-    const long chunks_total = (long)d.B * cps_t;
-    long cper = (chunks_total + d.nsplit - 1) / d.nsplit;
-    cper += cper & 1;                              // whole pairs (slab boundaries on 32-frame marks, as in wgrad_pc.hip; ldt % 32 == 0)
-    const long c_begin = (long)s * cper;
-    long c_end = c_begin + cper;
-    if (c_end > chunks_total) c_end = chunks_total;
-    const int nk = (int)(c_end > c_begin ? c_end - c_begin : 0);      // even
+    long c_begin;
+    const int nk = slab_chunks((long)d.B * cps_t, d.nsplit, true, s, c_begin);      // whole pairs: even
     const int np = nk >> 1;
 
     if (X_GLN) {
@@ -242,7 +198,7 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
         if (X_GLN) { xg = d.x_gamma[n0 + x_row]; xb = d.x_beta[n0 + x_row]; }
         asm volatile("" :: "v"(xg), "v"(xb), "v"(alpha_x));
         int cb = (int)(c_begin / cps_t), ct = (int)(c_begin % cps_t);
-        int xexp = W16UNSET;                                                     // this row's running scale exponent
+        int xexp = F16X3_UNSET;                                                  // this row's running scale exponent
 
         auto read8 = [&](const float* raw, const int par, const int row, const int half, float (&v)[8]) {      // chunk `par` of the pair
             const int f = w16_f8(row);
@@ -253,7 +209,7 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
         auto put8 = [&](float* planes, const int row, const int half, const float (&v)[8]) {
             unsigned hi[4], lo[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) w16_split2_pair(v[2 * q], v[2 * q + 1], hi[q], lo[q]);
+            for (int q = 0; q < 4; ++q) split2_pair_mix(v[2 * q], v[2 * q + 1], hi[q], lo[q]);
             float* base = planes + (size_t)(2 * half) * TN * 4 + row * 4;
             *reinterpret_cast<u32x4_t*>(base) = u32x4_t{hi[0], hi[1], hi[2], hi[3]};
             *reinterpret_cast<u32x4_t*>(base + TN * 4) = u32x4_t{lo[0], lo[1], lo[2], lo[3]};
@@ -288,8 +244,8 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
                 }
                 m = fmaxf(m, w16_amax8(v[h]));
             }
-            if (!X_FULL) m = w16_max_neighbour(m);                     // the row's other eight frames sit in the neighbouring lane
-            xexp = w16_next_exp(m, xexp);
+            if (!X_FULL) m = max_lane_xor1(m);                     // the row's other eight frames sit in the neighbouring lane
+            xexp = f16x3_next_exp(m, xexp);
 #pragma unroll
             for (int h = 0; h < (X_FULL ? 2 : 1); ++h) {
 #pragma unroll
@@ -314,10 +270,10 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
         if (np > 0) { issueG(); issueX(); }
         if (np > 1) { issueG(); issueX(); }
         if (np > 2) issueG();
-        if (np > 2) w16_wait_barrier<2 * PG + PX>();                             // B_-2: raw pair 0 landed (behind it: G1 X1 G2)
-        else w16_wait_barrier<0>();
+        if (np > 2) wait_vm_barrier<2 * PG + PX>();                             // B_-2: raw pair 0 landed (behind it: G1 X1 G2)
+        else wait_vm_barrier<0>();
         if (nk > 0) process(0);
-        w16_lgkm0_barrier();                                                     // B_-1: the operands of chunk 0
+        lgkm0_barrier();                                                     // B_-1: the operands of chunk 0
 
         for (int j = 0; j < nk; ++j) {
             const int P = j >> 1;
@@ -325,11 +281,11 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
             if (!(j & 1)) {
                 // chunk j + 2 opens pair P + 1: landed -- mine: all but the G pair fetched after it; everyone's: the barrier.  The X stage
                 // of pair P has been read for the last time (chunk j + 1, just now) and takes the pair after next.
-                if (P + 2 < np) w16_wait_barrier<PG>(); else w16_wait_barrier<0>();
+                if (P + 2 < np) wait_vm_barrier<PG>(); else wait_vm_barrier<0>();
                 W16STAMP(1, 3);
                 if (P + 2 < np) issueX();
             } else {
-                w16_lgkm0_barrier();
+                lgkm0_barrier();
                 W16STAMP(1, 3);
                 if (P + 3 < np) issueG();                                       // (raw G of pair P was read for the last time in step j - 1)
             }
@@ -353,11 +309,11 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
         u32x4_t sa[2][2][2], sb[2][2][2];                                        // sa[parity][mi][hi, lo]; sb[h][n][hi, lo]
         float ra[2][8];                                                          // raw G: [mi][frame 8*lk + e] of row 64*wr + 32*mi + l31
         float bias_acc[2] = {0.f, 0.f};
-        int gexp[2] = {W16UNSET, W16UNSET};                                      // running scale exponents of this lane's two G rows
+        int gexp[2] = {F16X3_UNSET, F16X3_UNSET};                                // running scale exponents of this lane's two G rows
         if (G2PRE) gexp[1] = d.g2_exps[(size_t)(c_begin / cps_t) * (d.M - d.g_split) + (m0 + 128 - d.g_split) + 32 * wr + l31];      // (the slab lies in ONE sample: checked by the launcher)
         int gdelta[2] = {0, 0};                                                  // their change with the chunk split last: applied to the accumulators
                                                                                  // before that chunk's first MFMA
-        int bcur[2][2] = {{W16UNSET, W16UNSET}, {W16UNSET, W16UNSET}};           // scale the accumulators of column block (h, n) are in
+        int bcur[2][2] = {{F16X3_UNSET, F16X3_UNSET}, {F16X3_UNSET, F16X3_UNSET}};      // scale the accumulators of column block (h, n) are in
         int en[2][2];
         const int g_f = w16_f8(l31);
         // Row blocks of the 256-row tile by wave: block mi = 0 of wave wr is rows 32 wr + [0, 32), block mi = 1 rows 128 + 32 wr + [0, 32) -- with a two-source G
@@ -386,7 +342,7 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
             bias_acc[mi] += (do_bias && live) ? rsum : 0.f;
             float m = w16_amax8(ra[mi]);
             m = w16_max_halves(m);                                               // the row's other eight frames: lane + 32
-            const int nexp = live ? w16_next_exp(m, gexp[mi]) : gexp[mi];
+            const int nexp = live ? f16x3_next_exp(m, gexp[mi]) : gexp[mi];
             gdelta[mi] = nexp - gexp[mi];
             gexp[mi] = nexp;
             asm volatile("" : "+v"(gdelta[mi]), "+v"(gexp[mi]));                 // materialise HERE (pure arithmetic is otherwise sunk past the MFMAs)
@@ -402,7 +358,7 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
                 W16_SB();
                 return;
             }
-            w16_split2_pair(__builtin_ldexpf(ra[mi][2 * q], gexp[mi]), __builtin_ldexpf(ra[mi][2 * q + 1], gexp[mi]), hi, lo);
+            split2_pair_mix(__builtin_ldexpf(ra[mi][2 * q], gexp[mi]), __builtin_ldexpf(ra[mi][2 * q + 1], gexp[mi]), hi, lo);
             sa[par][mi][0][q] = hi;
             sa[par][mi][1][q] = lo;
             asm volatile("" : "+v"(sa[par][mi][0]), "+v"(sa[par][mi][1]));
@@ -457,7 +413,7 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
         auto M = [&](auto parc, auto hc, auto kc) __attribute__((always_inline)) {
             constexpr int par = decltype(parc)::value, h = decltype(hc)::value, k = decltype(kc)::value;
             constexpr int part = k >> 2, mi = (k >> 1) & 1, n = k & 1;
-            acc[h][mi][n] = w16_mfma(sa[par][mi][part == 1 ? 1 : 0], sb[h][n][part == 0 ? 1 : 0], acc[h][mi][n]);
+            acc[h][mi][n] = mfma_f16(sa[par][mi][part == 1 ? 1 : 0], sb[h][n][part == 0 ? 1 : 0], acc[h][mi][n]);
             W16_SB();
         };
 #define W16_I(k) std::integral_constant<int, (k)>{}
@@ -504,7 +460,7 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
             W16_SB();
         };
         __syncthreads();                                                         // (the producers' table barrier)
-        w16_lgkm0_barrier();                                                     // B_-2: raw pair 0 has landed
+        lgkm0_barrier();                                                     // B_-2: raw pair 0 has landed
         int gstage = 0;
         if (nk > 0) {                                                            // chunk 0 is scaled and split up front
             read_raw_mi(0, W16_I(0), W16_I(0)); read_raw_mi(0, W16_I(0), W16_I(1));
@@ -513,12 +469,12 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
             split_pair(W16_I(0), W16_I(1), W16_I(0)); split_pair(W16_I(0), W16_I(1), W16_I(1)); split_pair(W16_I(0), W16_I(1), W16_I(2)); split_pair(W16_I(0), W16_I(1), W16_I(3));
             read_raw_mi(0, W16_I(1), W16_I(0)); read_raw_mi(0, W16_I(1), W16_I(1));      // chunk 1 (same pair): split during step 0
         }
-        w16_lgkm0_barrier();                                                     // B_-1: the X operands of chunk 0 are there
+        lgkm0_barrier();                                                     // B_-1: the X operands of chunk 0 are there
         load_b(0, W16_I(0));
         int buf = 0;
         for (int j = 0; j < nk; j += 2) {
             W16STAMP(0, 0);
-            w16_lgkm0_barrier();                                                 // B_j: the X operands of chunk j+1 are there, the raw pair of chunk j+2 too
+            lgkm0_barrier();                                                 // B_j: the X operands of chunk j+1 are there, the raw pair of chunk j+2 too
             W16STAMP(0, 1);
             const int gnext = gstage + 1 == W16NGP ? 0 : gstage + 1;            // stage of the NEXT pair: chunks j+2 and j+3
             int nb = buf + 1 == W16NXB ? 0 : buf + 1;
@@ -526,7 +482,7 @@ __device__ __forceinline__ void w16_body(const sep_wgrad_desc& d, const int bid)
             buf = nb;
             W16STAMP(0, 2);
             if (j + 1 < nk) {
-                w16_lgkm0_barrier();                                             // B_{j+1}
+                lgkm0_barrier();                                             // B_{j+1}
                 W16STAMP(0, 3);
                 nb = buf + 1 == W16NXB ? 0 : buf + 1;
                 step(W16_I(1), j + 2 < nk, buf, nb, gnext);
@@ -601,7 +557,7 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc16_kernel(const sep_wgrad_d
 constexpr int W16_MAXBATCH = 8;
 struct W16Batch {
     sep_wgrad_desc d;                       // the common shape / prologue; its operand pointers are replaced per product
-    int per;                                // workgroups per product (a multiple of 8: the XCD decode of the body sees bid & 7 = blockIdx & 7)
+    int per;                                // workgroups per product (xcd_grid: a multiple of 8, so the body's xcd_decode sees the XCD the block really runs on)
     const float* G[W16_MAXBATCH];
     const float* G2[W16_MAXBATCH];
     const float* X[W16_MAXBATCH];
@@ -619,7 +575,7 @@ __global__ __launch_bounds__(512, 2) void pw_wgrad_pc16_batch_kernel(const W16Ba
 template <int WR, int WC, int XMODE, bool G2PRE = false>
 void launch_w16(const sep_wgrad_desc& d, hipStream_t stream, const char* name) {
     const int ntiles = (d.M / (64 * WR)) * (d.N / (128 * WC));
-    const int grid = 8 * ntiles * ceil_div(d.nsplit, 8);
+    const int grid = xcd_grid(ntiles, d.nsplit);
     sep_set_kernel(name);                                                      // sep_last_kernel()
     hipLaunchKernelGGL((pw_wgrad_pc16_kernel<WR, WC, XMODE, G2PRE>), dim3(grid), dim3(512), 0, stream, d);
 }
@@ -646,9 +602,7 @@ int sep_pw_wgrad_pc16(const sep_wgrad_desc* d, hipStream_t stream) {
     // second G source handed over PRE-SPLIT (sep_split_rows): the heads' [dout; dS] with dS split once per step for all layers.  One 256-row tile
     // (M = 256, g_split = 128), slabs inside one sample (the row scales are per sample), the bias partials of those rows come with it.
     if (d->G2_pre != nullptr) {
-        const long cps_t = d->ldt / DK, chunks_total = (long)d->B * cps_t;
-        long cper = (chunks_total + d->nsplit - 1) / d->nsplit;
-        cper += cper & 1;
+        const long cps_t = d->ldt / DK, cper = slab_cper((long)d->B * cps_t, d->nsplit, true);
         if (!(d->M == 256 && d->g_split == 128 && d->g2_exps && (d->g2_sums || !d->partial_bias) && cps_t % cper == 0 &&
               (d->x_mode == SEP_PRO_PRELU || d->x_mode == SEP_PRO_NONE)))
             return 0;
@@ -671,7 +625,7 @@ int sep_pw_wgrad_pc16_batch(const sep_wgrad_desc* ds, int n, hipStream_t stream)
     W16Batch b;
     b.d = ds[0];
     const int ntiles = (ds[0].M / 256) * (ds[0].N / 128);
-    b.per = 8 * ntiles * ceil_div(ds[0].nsplit, 8);
+    b.per = xcd_grid(ntiles, ds[0].nsplit);
     for (int k = 0; k < W16_MAXBATCH; ++k) {
         const sep_wgrad_desc& q = ds[k < n ? k : 0];
         b.G[k] = q.G; b.G2[k] = q.G2; b.X[k] = q.X; b.partial[k] = q.partial; b.partial_bias[k] = q.partial_bias;

@@ -80,6 +80,28 @@ def test_the_ledger_lists_every_launch_line_of_the_dispatchers():
     assert len(GM.INSTANCES) == 28 + 2 * (28 + 3) + (14 * 3 + 2) + 18 + 1
 
 
+def test_the_split_arithmetic_and_the_block_decode_are_spelled_in_one_file():
+    """the primitives of SEP_ARITH_F16X3 / SEP_ARITH_BF16X6 (the mixed-precision FMA of the two-part split, the two MFMA builtins, the byte
+    selector of the three-part split) and the XCD-aware block decode occur in csrc/gemm_common.hpp and in no other file of csrc/ -- as
+    code or as comment --, the float4 load in csrc/common.hpp alone: a second copy under another name would be found here.  The one
+    exception: pw_wgrad_split_kernel and pw_wgrad_direct_kernel (gemm.hip) spell the decode out, once each, because their generated code
+    changes behind the helper -- exactly two occurrences there, so a third copy is still found"""
+    csrc = os.path.join(ROOT, "dnn-based_source_separation_amd", "csrc")
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if os.path.isfile(os.path.join(csrc, f))}
+    assert {"common.hpp", "gemm_common.hpp", "gemm.hip", "gemm_coop.hip", "gemm_pc.hip", "wgrad_pc.hip", "wgrad_pc16.hip", "stream.hip", "cln.hip"} <= set(texts)
+    once = {"v_fma_mix_f32": "gemm_common.hpp",
+            "__builtin_amdgcn_mfma_f32_32x32x16_f16(": "gemm_common.hpp",
+            "__builtin_amdgcn_mfma_f32_32x32x16_bf16(": "gemm_common.hpp",
+            "0x07060302u": "gemm_common.hpp",
+            "float4 ld4(": "common.hpp"}
+    for spelling, home in once.items():
+        assert [f for f, t in texts.items() if spelling in t] == [home], spelling
+    assert {f: t.count("bid & 7") for f, t in texts.items() if "bid & 7" in t} == {"gemm_common.hpp": 1, "gemm.hip": 2}
+    for kernel in ("pw_wgrad_direct_kernel", "pw_wgrad_split_kernel"):          # ... and the two are where they are said to be
+        body = texts["gemm.hip"].split("void %s(const sep_wgrad_desc d) {" % kernel)[1]
+        assert "bid & 7" in body[:body.index("__syncthreads()")], kernel
+
+
 def _one_case(sim_library, perturb):
     import sepkernels
     c = dict(GM.cases("default", "host")[1])          # the heads' form on the producer / consumer kernel

@@ -21,39 +21,35 @@ FILES = ("stream", "cln", "loss", "lstm", "linear", "attn", "rownorm", "gemm", "
 _DYN = re.compile(r"extern __shared__ (?:__attribute__\(\(aligned\(\d+\)\)\) )?(\w+) (\w+)\[\];")
 
 # The GEMM files: helper functions whose bodies are inline assembly (or address-space casts) get a C++ body in the compiled copies.
-_SPLIT2 = """static inline void {n}(const float x0, const float x1, unsigned& hi, unsigned& lo) {{
+_SPLIT2 = """static inline void split2_pair_mix(const float x0, const float x1, unsigned& hi, unsigned& lo) {
     const fp16x2_t h = __builtin_amdgcn_cvt_pkrtz(x0, x1);
     hi = __builtin_bit_cast(unsigned, h);
     _Float16 hh[2]; memcpy(hh, &hi, 4);
     lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x0 - (float)hh[0], x1 - (float)hh[1]));      // v_fma_mix_f32: exact in fp32
-}}
+}
 """
 _HELPERS = {
     "gemm_common.hpp": [
         ("glds16_asm", "static inline void glds16_asm(const float* base, unsigned voff, unsigned lds_dst) { sim_glds16((const char*)base + voff, lds_dst); }\n"),
         ("glds16_asm_v", "static inline void glds16_asm_v(const float* gsrc, unsigned lds_dst) { sim_glds16(gsrc, lds_dst); }\n"),
-        ("lds_addr", "static inline unsigned lds_addr(const float* p) { return sim_lds_addr(p); }\n")],
+        ("lds_addr", "static inline unsigned lds_addr(const float* p) { return sim_lds_addr(p); }\n"),
+        ("split2_pair_mix", _SPLIT2),
+        ("vmax_raw", "static inline float vmax_raw(const float a, const float b) { return a > b ? a : b; }\n"),
+        ("max_lane_xor1", "static inline float max_lane_xor1(const float m) { const float o = sim_read_lane(m, (threadIdx.x & 63) ^ 1); return m > o ? m : o; }\n")],
     "gemm_pc.hip": [
         # the flag protocol between producer and consumer waves rests on the LDS executing ONE WAVE's accesses in order (every lane's panel
         # write precedes the wave's flag store).  Lanes are threads here: the wave meets before its flag store, and the flags are atomics.
         ("pcd_load4", "static inline pcd_i4 pcd_load4(const int* c) { pcd_i4 v; for (int i = 0; i < 4; ++i) v[i] = __atomic_load_n(c + i, __ATOMIC_ACQUIRE); return v; }\n"),
-        ("pcd_post", "static inline void pcd_post(int* c, const int value) { sim_wave_sync(); __atomic_store_n(c, value, __ATOMIC_RELEASE); }\n"),
-        ("pcd_vmax", "static inline float pcd_vmax(const float a, const float b) { return a > b ? a : b; }\n"),
-        ("pcd_max_quad_neighbour", "static inline float pcd_max_quad_neighbour(const float m) { const float o = sim_read_lane(m, (threadIdx.x & 63) ^ 1); return m > o ? m : o; }\n"),
-        ("pcd_split2_pair", _SPLIT2.format(n="pcd_split2_pair"))],
+        ("pcd_post", "static inline void pcd_post(int* c, const int value) { sim_wave_sync(); __atomic_store_n(c, value, __ATOMIC_RELEASE); }\n")],
     "wgrad_pc16.hip": [
         ("w16_max_halves", "static inline float w16_max_halves(const float m) { const float o = sim_read_lane(m, (threadIdx.x & 63) ^ 32); return m > o ? m : o; }\n"),
-        ("w16_max_neighbour", "static inline float w16_max_neighbour(const float m) { const float o = sim_read_lane(m, (threadIdx.x & 63) ^ 1); return m > o ? m : o; }\n"),
-        ("w16_split2_pair", _SPLIT2.format(n="w16_split2_pair")),
         ("w16_dma_pieces8", "static inline void w16_dma_pieces8(const float* pa, const float* pb, const unsigned (&voffc)[8], unsigned lds1) { for (int q = 0; q < 8; ++q) "
                             "sim_glds16((const char*)(q < 4 ? pa : pb) + voffc[q] - ((q & 1) ? 0 : 4096), lds1 + 4096 * (q - 1)); }\n"),
         ("w16_dma_pieces4", "static inline void w16_dma_pieces4(const float* pa, const unsigned (&voffc)[4], unsigned lds1) { for (int q = 0; q < 4; ++q) "
                             "sim_glds16((const char*)pa + voffc[q] - ((q & 1) ? 0 : 4096), lds1 + 4096 * (q - 1)); }\n")],
     "gemm_coop.hip": [
-        ("co_vmax", "static inline float co_vmax(const float a, const float b) { return a > b ? a : b; }\n"),
         ("co_quad_max", "static inline float co_quad_max(const float m) { float o = sim_read_lane(m, (threadIdx.x & 63) ^ 1); const float t = m > o ? m : o; "
-                        "o = sim_read_lane(t, (threadIdx.x & 63) ^ 2); return t > o ? t : o; }\n"),
-        ("co_split2_pair", _SPLIT2.format(n="co_split2_pair"))],
+                        "o = sim_read_lane(t, (threadIdx.x & 63) ^ 2); return t > o ? t : o; }\n")],
 }
 
 

@@ -1,5 +1,6 @@
-// Development tool: the single-instruction helpers of csrc/wgrad_pc16.hip on the device (the host simulation replaces them by C++):
-// w16_max_halves (v_permlane32_swap), w16_max_neighbour (v_max_f32_dpp), w16_split2_pair (v_fma_mix_f32).
+// Development tool: the single-instruction helpers of the scaled fp16 weight gradient on the device (the host simulation replaces them
+// by C++), as local copies: w16_max_halves of csrc/wgrad_pc16.hip (v_permlane32_swap), and under their former names w16_max_neighbour =
+// max_lane_xor1 (v_max_f32_dpp) and w16_split2_pair = split2_pair_mix (v_fma_mix_f32) of csrc/gemm_common.hpp.
 //   hipcc --offload-arch=gfx950 -O3 -o /tmp/w16_probe tools/w16_probe.hip && /tmp/w16_probe
 #include <hip/hip_runtime.h>
 #include <stdio.h>
