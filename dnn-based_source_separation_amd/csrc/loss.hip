@@ -646,6 +646,152 @@ extern "C" int sep_bss_energies(const float* ref, const float* est, const double
     return 0;
 }
 
+// ---- BSS-eval v4 ("images"): the framewise decomposition pass of museval's SDR / ISR / SIR / SAR ---------------------------------------------
+// Reference arithmetic replaced: museval.eval_mus_track, where the reference's music tester ends (egs/musdb18/conv-tasnet/src/adhoc_driver.py:
+// 352-380).  The filters are the caller's (utils/bss.py: sep_bss_xcorr on (B, n C, T) views, one dense solve per row); this pass applies them to
+// every frame's segment alone -- samples outside the frame count as zero -- and forms the seven energies and the two silence counts of a
+// (frame, source).  The rules of the v3 kernels hold: no atomics, slabs of FIXED size counted from the frame's first sample, partials added in
+// ascending order by bss_reduce_kernel, 64-bit offsets, the projected signals in registers only.
+namespace {
+
+constexpr int BSS_IM_SLAB = 1024;       // output samples of a frame behind one partial of sep_bss_image_energies
+constexpr int BSS_IM_SUMS = 9;
+
+__device__ __forceinline__ int bss_row_frames(const int Tb, const int window, const int hop, const int nwin) {
+    if (Tb < window) return 0;
+    const int64_t f = ((int64_t)Tb - window + hop) / hop;               // every frame is full: (f - 1) hop + window <= Tb
+    return f < nwin ? (int)f : nwin;
+}
+
+// Frame w of source j of sample b, output samples [slab BSS_IM_SLAB, (slab + 1) BSS_IM_SLAB) of the frame's window + flen - 1: thread `tid` of a
+// step owns t = t0 + tid and forms, for every channel c in turn, P_all[t] = sum_{kc} sum_tau fa[j][c][kc][tau] r_w[kc][t - tau] in ONE walk over
+// the n C reference channels; the C channels of source j feed P_j[t] = sum_{c2} sum_tau fo[j][c][c2][tau] r_w[j][c2][t - tau] from the same
+// staged tile.  r_s[q] = r_w[t0 - tau0 - (BSS_TILE - 1) + q] with r_w zero outside [0, window): the tap tau0 + x of thread tid reads
+// r_s[tid + BSS_TILE - 1 - x] -- consecutive doubles across the wave, the taps broadcasts.  A frame beyond the row's own count writes zeros.
+// grid (nslab, n nwin, B).
+__global__ __launch_bounds__(256) void bss_image_energies_kernel(const float* __restrict__ ref, const float* __restrict__ est,
+                                                                 const double* __restrict__ filt_all, const double* __restrict__ filt_one,
+                                                                 double* __restrict__ part, const int32_t* __restrict__ lengths, const int n,
+                                                                 const int C, const int T, const int flen, const int window, const int hop,
+                                                                 const int nwin, const int nslab) {
+    __shared__ double r_s[2 * BSS_TILE];
+    __shared__ double f_s[BSS_TILE];
+    __shared__ double g_s[BSS_TILE];
+    __shared__ double red[4];
+    const int tid = threadIdx.x, b = blockIdx.z, j = blockIdx.y / nwin, w = blockIdx.y % nwin, slab = blockIdx.x;
+    double* po = part + ((((int64_t)b * n + j) * nwin + w) * nslab + slab) * BSS_IM_SUMS;
+    if (w >= bss_row_frames(bss_row_length(lengths, b, T), window, hop, nwin)) {           // (the same for the whole workgroup)
+        if (tid < BSS_IM_SUMS) po[tid] = 0.0;
+        return;
+    }
+    const int nc = n * C;
+    const int64_t Wx = (int64_t)window + flen - 1, origin = (int64_t)w * hop;              // origin + window <= T_b
+    const int64_t t_end = (int64_t)(slab + 1) * BSS_IM_SLAB < Wx ? (int64_t)(slab + 1) * BSS_IM_SLAB : Wx;
+    const float* rb = ref + (int64_t)b * nc * T + origin;
+    const float* eb = est + ((int64_t)b * n + j) * C * T + origin;
+    double v[BSS_IM_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t t0 = (int64_t)slab * BSS_IM_SLAB; t0 < t_end; t0 += BSS_TILE) {
+        const int64_t t = t0 + tid;
+        double rsum = 0.0, esum = 0.0;
+        for (int c = 0; c < C; ++c) {
+            double pall = 0.0, pj = 0.0;
+            for (int kc = 0; kc < nc; ++kc) {
+                const bool own = kc / C == j;
+                const float* rr = rb + (int64_t)kc * T;
+                const double* fa = filt_all + ((((int64_t)b * n + j) * C + c) * nc + kc) * flen;
+                const double* fo = filt_one + ((((int64_t)b * n + j) * C + c) * C + (own ? kc - j * C : 0)) * flen;
+                for (int tau0 = 0; tau0 < flen; tau0 += BSS_TILE) {
+                    const int nx = flen - tau0 < BSS_TILE ? flen - tau0 : BSS_TILE;
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int q = tid + h * BSS_TILE;
+                        const int64_t u = t0 - tau0 - (BSS_TILE - 1) + q;
+                        r_s[q] = (u >= 0 && u < window) ? (double)rr[u] : 0.0;
+                    }
+                    f_s[tid] = tid < nx ? fa[tau0 + tid] : 0.0;
+                    if (own) g_s[tid] = tid < nx ? fo[tau0 + tid] : 0.0;
+                    __syncthreads();
+                    if (own) {
+#pragma unroll 4
+                        for (int x = 0; x < nx; ++x) {
+                            const double r = r_s[tid + BSS_TILE - 1 - x];
+                            pall = fma(f_s[x], r, pall);
+                            pj = fma(g_s[x], r, pj);
+                        }
+                    } else {
+#pragma unroll 4
+                        for (int x = 0; x < nx; ++x) pall = fma(f_s[x], r_s[tid + BSS_TILE - 1 - x], pall);
+                    }
+                    __syncthreads();
+                }
+            }
+            if (t < Wx) {
+                const bool in = t < window;
+                const double s = in ? (double)rb[((int64_t)j * C + c) * T + t] : 0.0, e = in ? (double)eb[(int64_t)c * T + t] : 0.0;
+                const double d = e - s, sp = pj - s, it = pall - pj, ar = e - pall;
+                v[0] = fma(s, s, v[0]);
+                v[1] = fma(d, d, v[1]);
+                v[2] = fma(sp, sp, v[2]);
+                v[3] = fma(pj, pj, v[3]);
+                v[4] = fma(it, it, v[4]);
+                v[5] = fma(pall, pall, v[5]);
+                v[6] = fma(ar, ar, v[6]);
+                rsum += s;
+                esum += e;
+            }
+        }
+        if (t < window) {
+            v[7] += rsum != 0.0 ? 1.0 : 0.0;
+            v[8] += esum != 0.0 ? 1.0 : 0.0;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < BSS_IM_SUMS; ++q) {
+        const double r = block_sum_256<double>(v[q], red);
+        if (tid == 0) po[q] = r;
+    }
+}
+
+// doubles of scratch the call needs, or -1 where a grid limit is exceeded
+static int64_t bss_image_scratch(const int B, const int n, const int flen, const int window, const int nwin) {
+    const int64_t nslab = bss_slabs((int64_t)window + flen - 1, BSS_IM_SLAB);
+    if ((int64_t)n * nwin > 65535 || B > 65535) return -1;
+    return (int64_t)B * n * nwin * nslab * BSS_IM_SUMS;                // < 2^16 2^16 2^21 9
+}
+static bool bss_image_shape_ok(const int B, const int n, const int C, const int flen, const int window, const int nwin) {
+    return B >= 1 && n >= 1 && C >= 1 && (int64_t)n * C <= 65535 && flen >= 1 && flen <= BSS_MAX_T && window >= 1 && window <= BSS_MAX_T && nwin >= 1;
+}
+
+}  // namespace
+
+extern "C" size_t sep_bss_image_scratch_bytes(int B, int n, int C, int flen, int window, int nwin) {
+    if (!bss_image_shape_ok(B, n, C, flen, window, nwin)) return 0;
+    const int64_t need = bss_image_scratch(B, n, flen, window, nwin);
+    return need < 0 ? 0 : (size_t)need * sizeof(double);
+}
+
+extern "C" int sep_bss_image_energies(const float* ref, const float* est, const double* filt_all, const double* filt_one, const int32_t* lengths,
+                                      double* out, double* scratch, size_t scratch_bytes, int B, int n, int C, int T, int flen, int window, int hop,
+                                      int nwin, sep_stream_t stream) {
+    SEP_REQUIRE(ref && est && filt_all && filt_one && out && scratch, "sep_bss_image_energies: null pointer");
+    SEP_REQUIRE(bss_image_shape_ok(B, n, C, flen, window, nwin) && T >= 1 && T <= BSS_MAX_T && hop >= 1 && hop <= BSS_MAX_T,
+                "sep_bss_image_energies: bad arguments (B=%d n=%d C=%d T=%d flen=%d window=%d hop=%d nwin=%d; all >= 1, n C <= 65535, T, flen, window "
+                "and hop within 2^30)", B, n, C, T, flen, window, hop, nwin);
+    const int64_t need = bss_image_scratch(B, n, flen, window, nwin);
+    SEP_REQUIRE(need >= 0, "sep_bss_image_energies: grid limit (B <= 65535, n nwin <= 65535)");
+    SEP_REQUIRE(scratch_bytes / sizeof(double) >= (size_t)need, "sep_bss_image_energies: scratch holds %zu bytes, %lld needed", scratch_bytes,
+                (long long)need * (long long)sizeof(double));
+    const int nslab = (int)bss_slabs((int64_t)window + flen - 1, BSS_IM_SLAB);
+    hipLaunchKernelGGL(bss_image_energies_kernel, dim3((unsigned)nslab, (unsigned)(n * nwin), (unsigned)B), dim3(256), 0, (hipStream_t)stream, ref, est,
+                       filt_all, filt_one, scratch, lengths, n, C, T, flen, window, hop, nwin, nslab);
+    SEP_CHECK_LAUNCH("sep_bss_image_energies");
+    const int64_t total = (int64_t)B * n * nwin * BSS_IM_SUMS;
+    hipLaunchKernelGGL(bss_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, out, nslab,
+                       BSS_IM_SUMS, total);
+    SEP_CHECK_LAUNCH("sep_bss_image_energies (reduction)");
+    return 0;
+}
+
 // ---- Mixture invariant training (MixIT) ---------------------------------------------------------------------------------------------------
 // The reference has no arithmetic to replace here: src/criterion/mixit.py is a stub that raises NotImplementedError.  The criterion is the one
 // of Wisdom et al. 2020: the best of the N^M ways to hand each of M estimates to one of N reference mixtures.  Every measure this library

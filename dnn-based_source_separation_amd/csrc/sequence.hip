@@ -70,7 +70,7 @@ const seq_entry SEQ_TABLE[] = {
     SEQ_FN(sep_cln_stats), SEQ_FN(sep_depthwise_cln_fwd), SEQ_FN(sep_depthwise_cln_bwd_weight), SEQ_FN(sep_sum_f64),
     SEQ_FN(sep_unfold_dilated), SEQ_FN(sep_fold_dilated), SEQ_FN(sep_online_unfold_fwd), SEQ_FN(sep_online_unfold_fwd_sel), SEQ_FN(sep_online_unfold_fwd_rag),
     SEQ_FN(sep_online_state_export), SEQ_FN(sep_online_state_import),
-    SEQ_FN(sep_bss_xcorr), SEQ_FN(sep_bss_energies),
+    SEQ_FN(sep_bss_xcorr), SEQ_FN(sep_bss_energies), SEQ_FN(sep_bss_image_energies),
     SEQ_FN(sep_mixit_gram), SEQ_FN(sep_mixit_search), SEQ_FN(sep_mixit_bwd),
     SEQ_FN(sep_pair_gram), SEQ_FN(sep_assign), SEQ_FN(sep_pair_assign), SEQ_FN(sep_pair_bwd),
     SEQ_FN(sep_stitch_cost), SEQ_FN(sep_stitch_chain), SEQ_FN(sep_stitch_ola),

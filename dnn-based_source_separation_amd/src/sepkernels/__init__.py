@@ -240,6 +240,9 @@ SIGNATURES = {
     "sep_bss_scratch_bytes": [_I] * 5,                               # returns size_t
     "sep_bss_xcorr": [_vp] * 5 + [ctypes.c_size_t] + [_I] * 6 + [_vp],
     "sep_bss_energies": [_vp] * 7 + [ctypes.c_size_t] + [_I] * 5 + [_vp],
+    # BSS-eval v4 "images" (ABI 23, additive): the framewise multichannel decomposition pass of museval's SDR, ISR, SIR, SAR
+    "sep_bss_image_scratch_bytes": [_I] * 6,                         # returns size_t
+    "sep_bss_image_energies": [_vp] * 7 + [ctypes.c_size_t] + [_I] * 8 + [_vp],
     # mixture invariant training (ABI 23, additive): the Gram matrix of estimates and mixtures, the search over the N^M assignments, the gradient
     "sep_mixit_scratch_bytes": [_I] * 4,                             # returns size_t
     "sep_mixit_gram": [_vp] * 4 + [ctypes.c_size_t] + [_I] * 4 + [_vp],
@@ -260,7 +263,7 @@ SIGNATURES = {
     "sep_resample_stream_fwd": [_vp] * 6 + [_I] * 7 + [_vp],
 }
 _RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_last_kernel": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
-             "sep_gln_tokens_ws_bytes": ctypes.c_size_t, "sep_online_state_row_bytes": ctypes.c_size_t, "sep_bss_scratch_bytes": ctypes.c_size_t,
+             "sep_gln_tokens_ws_bytes": ctypes.c_size_t, "sep_online_state_row_bytes": ctypes.c_size_t, "sep_bss_scratch_bytes": ctypes.c_size_t, "sep_bss_image_scratch_bytes": ctypes.c_size_t,
              "sep_mixit_scratch_bytes": ctypes.c_size_t, "sep_pair_gram_scratch_bytes": ctypes.c_size_t}
 
 _lib = None
@@ -929,6 +932,15 @@ class HipBackend:
     def bss_energies(self, ref, est, filt_all, filt_one, lengths, out, scratch, B, n, m, T, flen):
         _check(load().sep_bss_energies(_ptr(ref, _f32), _ptr(est, _f32), _ptr(filt_all, _f64), _ptr(filt_one, _f64), _ptr(lengths, torch.int32),
                                        _ptr(out, _f64), _ptr(scratch, _f64), 8 * scratch.numel(), B, n, m, T, flen, _stream()), "sep_bss_energies")
+
+    # ... BSS-eval v4 "images": ref, est (B, n, C, T) fp32; filt_all (B, n, C, n C, flen), filt_one (B, n, C, C, flen), out (B, n, nwin, 9) fp64
+    def bss_image_scratch_bytes(self, B, n, C, flen, window, nwin):
+        return int(load().sep_bss_image_scratch_bytes(B, n, C, flen, window, nwin))
+
+    def bss_image_energies(self, ref, est, filt_all, filt_one, lengths, out, scratch, B, n, C, T, flen, window, hop, nwin):
+        _check(load().sep_bss_image_energies(_ptr(ref, _f32), _ptr(est, _f32), _ptr(filt_all, _f64), _ptr(filt_one, _f64), _ptr(lengths, torch.int32),
+                                             _ptr(out, _f64), _ptr(scratch, _f64), 8 * scratch.numel(), B, n, C, T, flen, window, hop, nwin, _stream()),
+               "sep_bss_image_energies")
 
     # ... mixture invariant training: est (B, M, T), tgt (B, N, T) fp32; gram (B, M + N, M + N) and scratch fp64 (scratch: mixit_scratch_bytes);
     # kind 0 SI-SDR, 1 SDR, 2 thresholded SNR; gw (B,) fp32 arrives at every per-mixture measure of an item (a mean's 1 / N folded in)

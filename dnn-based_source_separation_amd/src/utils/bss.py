@@ -15,6 +15,13 @@ signals are never stored.  Definition, for references r_i and estimates e_j of T
 SEPK_BSS_EVAL = auto (default) | native | mir_eval selects the route of `bss_eval_sources`: `auto` hands the call to mir_eval exactly as the
 reference's wrapper does when that package can be imported (a machine that has it keeps the reference's numbers) and runs the native route
 otherwise; `mir_eval` insists on the package.  An all-zero reference or estimate is a ValueError on either route.
+
+BSS-eval v4 ("images"), the framewise SDR, ISR, SIR and SAR that music separation is published with (museval 0.4's metrics.bss_eval as
+eval_mus_track calls it: window = hop = 1 s, 512 taps, filters from the whole recording, no permutation search), is `bss_eval_images_batch`,
+`bss_eval_images` and `eval_track` below; its definition stands in include/sepkernels.h at sep_bss_image_energies and in DESIGN.md 4.14.  The
+filters come from the same two sep_bss_xcorr calls on (B, n C, T) views and the same dense solve; sep_bss_image_energies applies them frame by
+frame.  These functions run the native route only, whatever SEPK_BSS_EVAL says: museval's own entry point takes a musdb track object and estimates
+of another layout, so handing a call over is not a few obvious lines, and the package is on none of the project's machines to check against.
 """
 import itertools
 import os
@@ -65,6 +72,27 @@ class _HostComposition:
             interf, artif = p_all[:, None] - s, (e - p_all)[:, None]
             for q, v in enumerate((s, interf, artif, interf + artif, s + interf)):
                 out[b, :, :, q] = v.square().sum(-1)
+
+    def bss_image_scratch_bytes(self, B, n, C, flen, window, nwin):
+        return 8
+
+    def bss_image_energies(self, ref, est, filt_all, filt_one, lengths, out, scratch, B, n, C, T, flen, window, hop, nwin):
+        conv = torch.nn.functional.conv1d
+        out.zero_()
+        for b in range(B):
+            Tb = T if lengths is None else int(lengths[b])
+            fa = filt_all[b].reshape(n * C, n * C, flen).flip(-1)                                        # [(j, c)][(k, c2)]
+            fo = filt_one[b].reshape(n * C, C, flen).flip(-1)                                            # [(j, c)][c2], group j
+            for w in range(min(nwin, _num_frames(Tb, window, hop))):
+                seg = slice(w * hop, w * hop + window)
+                s = torch.nn.functional.pad(ref[b, :, :, seg].double(), (0, flen - 1))                   # (n, C, W + flen - 1)
+                e = torch.nn.functional.pad(est[b, :, :, seg].double(), (0, flen - 1))
+                rp = torch.nn.functional.pad(s.reshape(1, n * C, -1), (flen - 1, 0))
+                p_all, p_j = conv(rp, fa)[0].reshape(n, C, -1), conv(rp, fo, groups=n)[0].reshape(n, C, -1)
+                for q, v in enumerate((s, e - s, p_j - s, p_j, p_all - p_j, p_all, e - p_all)):
+                    out[b, :, w, q] = v.square().sum((-2, -1))
+                out[b, :, w, 7] = (s[..., :window].sum(1) != 0).sum(-1).double()
+                out[b, :, w, 8] = (e[..., :window].sum(1) != 0).sum(-1).double()
 
 
 def _kernels(t):
@@ -249,3 +277,143 @@ def bss_eval_sources(reference_sources, estimated_sources, compute_permutation=T
         raise ValueError("reference_sources must be (n_sources, T)")
     sdr, sir, sar, perm = bss_eval_sources_batch(reference_sources[None], estimated_sources[None], compute_permutation=compute_permutation)
     return sdr[0], sir[0], sar[0], perm[0]
+
+
+# ---- BSS-eval v4 ("images"): framewise SDR, ISR, SIR, SAR as museval scores a MUSDB18 track ----------------------------------------------------
+IMAGE_METRICS = ("SDR", "ISR", "SIR", "SAR")
+
+
+def _num_frames(T, window, hop):
+    """full frames of `window` samples every `hop` in T samples: a trailing partial window is dropped"""
+    return max(0, (T - window + hop) // hop) if T >= window else 0
+
+
+def _image_kernels(t):
+    K, dev = _kernels(t)
+    if not hasattr(K, "bss_image_energies"):        # a backend object from before the images call: the composition on whatever device holds the data
+        K = _HostComposition()
+    return K, dev
+
+
+def _image_filters(xrr, xre, n, C, flen):
+    """xrr (B, n C, n C, 2 flen - 1), xre (B, n C, n C, flen) of the reference and estimate CHANNELS -> filt_all (B, n, C, n C, flen): [b][j][c][(k, c2)]
+    the filter on r[k][c2] in the projection of e[j][c] on every reference channel, from G (n C flen)^2 and D as in `_filters`; filt_one
+    (B, n, C, C, flen): [b][j][c][c2] the filter on r[j][c2] in its projection on the channels of reference j alone, from the diagonal
+    (C flen)^2 block of source j and the rows and columns of D that belong to it"""
+    B, nc = xrr.shape[:2]
+    dev = xrr.device
+    tau = torch.arange(flen, device=dev)
+    toeplitz = tau[:, None] - tau[None, :] + (flen - 1)
+    filt_all = torch.empty(B, n, C, nc, flen, device=dev, dtype=torch.float64)
+    filt_one = torch.empty(B, n, C, C, flen, device=dev, dtype=torch.float64)
+    for b in range(B):                              # one solve per row: a row's filters do not depend on the batch around it
+        G = xrr[b][:, :, toeplitz].permute(0, 2, 1, 3).reshape(nc * flen, nc * flen)
+        D = xre[b].permute(0, 2, 1).reshape(nc * flen, nc)             # [(k, c2, p)][(j, c)]
+        filt_all[b] = _solve(G, D).reshape(nc, flen, n, C).permute(2, 3, 0, 1)
+        own = [slice(j * C * flen, (j + 1) * C * flen) for j in range(n)]
+        Gj = torch.stack([G[own[j], own[j]] for j in range(n)])
+        Dj = torch.stack([D[own[j], j * C:(j + 1) * C] for j in range(n)])
+        filt_one[b] = _solve(Gj, Dj).reshape(n, C, flen, C).permute(0, 3, 1, 2)
+    return filt_all, filt_one
+
+
+def bss_image_energies_batch(reference, estimated, lengths=None, window=44100, hop=44100, filter_length=FILTER_LENGTH):
+    """reference, estimated (B, n, C, T) -> (B, n, nwin, 9) fp64 on the CPU, the sums of sep_bss_image_energies (include/sepkernels.h) of every
+    source and frame, and num_frames (B,) long; nwin is the largest frame count of the batch, rows with fewer frames hold zeros beyond theirs"""
+    if reference.dim() != 4 or reference.shape != estimated.shape:
+        raise ValueError("reference and estimated images must both be (B, n, C, T); got {} and {}".format(tuple(reference.shape), tuple(estimated.shape)))
+    B, n, C, T = reference.shape
+    flen, window, hop = int(filter_length), int(window), int(hop)
+    if flen < 1 or window < 1 or hop < 1 or B < 1 or n < 1 or C < 1 or T < 1:
+        raise ValueError("empty input, or filter_length, window or hop < 1")
+    K, dev = _image_kernels(reference)
+    ref = reference.detach().to(dev, torch.float32).contiguous()
+    est = estimated.detach().to(dev, torch.float32).contiguous()
+    if lengths is not None:
+        host = torch.as_tensor(lengths).to("cpu", torch.int64).reshape(-1)
+        if host.numel() != B or int(host.min()) < 1 or int(host.max()) > T:
+            raise ValueError("lengths must hold one value in [1, T] per row")
+        lengths = host.to(torch.int32).to(dev)
+        audible = ((ref != 0) & (torch.arange(T, device=dev) < lengths[:, None, None, None])).any(-1)
+    else:
+        host = torch.full((B,), T, dtype=torch.int64)
+        audible = (ref != 0).any(-1)
+    if not bool(audible.all()):
+        raise ValueError("a reference channel is all zeros: the projection on it is undefined")
+    num_frames = torch.tensor([_num_frames(int(t), window, hop) for t in host], dtype=torch.int64)
+    nwin = int(num_frames.max())
+    if nwin == 0:
+        return torch.zeros(B, n, 0, 9, dtype=torch.float64), num_frames
+    nc = n * C
+    nbytes = max(K.bss_scratch_bytes(B, nc, nc, T, flen), K.bss_image_scratch_bytes(B, n, C, flen, window, nwin))
+    scratch = torch.empty(max(1, nbytes // 8), device=dev, dtype=torch.float64)
+    xrr, xre = _correlations(K, ref.reshape(B, nc, T), est.reshape(B, nc, T), lengths, flen, scratch)
+    filt_all, filt_one = _image_filters(xrr, xre, n, C, flen)
+    del xrr, xre
+    out = torch.empty(B, n, nwin, 9, device=dev, dtype=torch.float64)
+    K.bss_image_energies(ref, est, filt_all, filt_one, lengths, out, scratch, B, n, C, T, flen, window, hop, nwin)
+    return out.cpu(), num_frames
+
+
+def bss_eval_images_batch(reference, estimated, lengths=None, window=44100, hop=44100, filter_length=FILTER_LENGTH):
+    """reference, estimated (B, n, C, T) or (B, n, T) on any device, rows of their own `lengths` (B values in [1, T]) if given; window and hop in
+    samples -> sdr, isr, sir, sar (B, n, nwin) fp64 on the CPU and num_frames (B,) long.  Estimate i is scored against reference i.  Row b has
+    num_frames[b] = max(0, (T_b - window + hop) // hop) frames (window > T_b: none, not an error), nwin is the largest of them, frames beyond a
+    row's own count are NaN; so is, for every source, a frame in which some reference or some estimate is silent (channel sum zero at every
+    sample).  A zero denominator gives +inf."""
+    if reference.dim() == 3 and estimated.dim() == 3:
+        reference, estimated = reference[:, :, None], estimated[:, :, None]
+    en, num_frames = bss_image_energies_batch(reference, estimated, lengths, window, hop, filter_length)
+    sdr, isr, sir, sar = _db(en[..., 0], en[..., 1]), _db(en[..., 0], en[..., 2]), _db(en[..., 3], en[..., 4]), _db(en[..., 5], en[..., 6])
+    silent = ((en[..., 7] == 0) | (en[..., 8] == 0)).any(1, keepdim=True)                # (B, 1, nwin): any source silent blanks the frame
+    beyond = torch.arange(en.shape[2])[None, None, :] >= num_frames[:, None, None]
+    nan = torch.full_like(sdr, float("nan"))
+    return tuple(torch.where(silent | beyond, nan, v) for v in (sdr, isr, sir, sar)) + (num_frames,)
+
+
+def bss_eval_images(reference, estimated, window=44100, hop=44100, filter_length=FILTER_LENGTH):
+    """one recording: reference, estimated (n, C, T) or (n, T) -> sdr, isr, sir, sar (n, nwin) fp64"""
+    if reference.dim() not in (2, 3):
+        raise ValueError("reference must be (n_sources, C, T) or (n_sources, T)")
+    return tuple(v[0] for v in bss_eval_images_batch(reference[None], estimated[None], None, window, hop, filter_length)[:4])
+
+
+def nanmedian(values):
+    """median of the values that are not NaN, the mean of the two middle ones for an even count (numpy.nanmedian); NaN if there are none"""
+    v = torch.as_tensor(values, dtype=torch.float64).reshape(-1)
+    v = v[~torch.isnan(v)].sort().values
+    k = v.numel()
+    if k == 0:
+        return float("nan")
+    lo, hi = v[(k - 1) // 2].item(), v[k // 2].item()
+    return lo if lo == hi else 0.5 * (lo + hi)       # (inf with inf stays inf instead of inf - inf games)
+
+
+def eval_track(references, estimates, rate, window_s=1.0, hop_s=1.0, filter_length=FILTER_LENGTH):
+    """references, estimates: dicts name -> (C, T) or (T,) tensor with the same names; rate in Hz.  museval.eval_mus_track's rule: the named stems
+    are scored jointly in one evaluation; when `vocals` is among them (with at least one more stem) a second evaluation of two sources,
+    `vocals` and `accompaniment` = the sum of the side's other stems, supplies the `accompaniment` rows and only those.
+    -> {target: {"frames": {"SDR": [...], "ISR": [...], "SIR": [...], "SAR": [...]}, "SDR": median, ...}}, frames as floats with NaN for silent
+    frames, medians over the frames that are not NaN."""
+    names = list(references)
+    if not names or set(names) != set(estimates):
+        raise ValueError("references and estimates must name the same, at least one, targets")
+    if "accompaniment" in names:
+        raise ValueError("`accompaniment` is formed here as the sum of the stems other than `vocals`; do not pass it")
+    image = lambda x: x[None] if x.dim() == 1 else x                   # noqa: E731
+    ref = torch.stack([image(references[k]) for k in names])
+    est = torch.stack([image(estimates[k]) for k in names]).to(ref.device)
+    window, hop = int(round(window_s * rate)), int(round(hop_s * rate))
+    scores = {}
+
+    def take(values, rows):
+        for name, i in rows:
+            frames = {m: values[q][i].tolist() for q, m in enumerate(IMAGE_METRICS)}
+            scores[name] = dict({"frames": frames}, **{m: nanmedian(frames[m]) for m in IMAGE_METRICS})
+    take(bss_eval_images(ref, est, window, hop, filter_length), [(k, i) for i, k in enumerate(names)])
+    if "vocals" in names and len(names) > 1:
+        v = names.index("vocals")
+        rest = [i for i in range(len(names)) if i != v]
+        pair = lambda x: torch.stack([x[v].double(), x[rest].double().sum(0)])      # noqa: E731  (summed in fp64, rounded to fp32 audio once)
+        take(bss_eval_images(pair(ref), pair(est), window, hop, filter_length), [("accompaniment", 1)])
+    return scores

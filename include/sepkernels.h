@@ -780,6 +780,43 @@ int sep_bss_xcorr(const float* a, const float* c, const int32_t* lengths, double
 int sep_bss_energies(const float* ref, const float* est, const double* filt_all, const double* filt_one, const int32_t* lengths, double* out,
                      double* scratch, size_t scratch_bytes, int B, int n, int m, int T, int flen, sep_stream_t stream);
 
+/* ---- BSS-eval v4 ("images"): museval's framewise SDR, ISR, SIR and SAR of music separation (ABI 23, additive; csrc/loss.hip) -------------------
+ * The figure music separation is published with, as museval 0.4's metrics.bss_eval computes it for eval_mus_track (window = hop = 1 s,
+ * filters_len = 512, framewise_filters = False, compute_permutation = False, images version; the reference's music tester ends there,
+ * egs/musdb18/conv-tasnet/src/adhoc_driver.py:352-380).  Restated from that code; agreement with the museval PACKAGE itself is untested, it is on
+ * none of the project's machines.  One recording has references r[i][c] and estimates e[j][c], i, j < n sources, c < C channels, T_b samples;
+ * filter length F = flen, window W, hop H.
+ *   Filters, once on the whole recording, every signal extended by F - 1 zeros: h_all[j][c][k][c2] (F taps each) minimises
+ *   |e[j][c] - sum_{k,c2} h_all[j][c][k][c2] * r[k][c2]|^2 over all n C reference channels, h_one[j][c][c2] the same over the C channels of
+ *   reference j alone.  Their normal equations are those of v3 above with n C rows in place of n: G is (n C F)^2 block Toeplitz from the lagged
+ *   correlations at lags -(F-1) .. F-1, D the correlations of the reference channels with the estimate channels at lags 0 .. F-1, h_one uses
+ *   the diagonal (C F)^2 block of source j.  sep_bss_xcorr computes both sets on (B, n C, T) views; the solves are the CALLER's (utils/bss.py).
+ *   Frames: row b has nwin_b = max(0, floor((T_b - W + H) / H)) frames, frame w covers samples [w H, w H + W): every frame is full, a trailing
+ *   partial window is dropped.  The decomposition is applied to the frame's segment ALONE: r_w, e_w are its W samples, samples outside the frame
+ *   count as zero even where the row has audio there, each segment is extended by F - 1 zeros.  For source j, per channel c:
+ *     s_true = r_w[j][c],  P_j = sum_{c2} h_one[j][c][c2] * r_w[j][c2],  P_all = sum_{k,c2} h_all[j][c][k][c2] * r_w[k][c2]   (* = convolution)
+ *     e_spat = P_j - s_true,  e_interf = P_all - P_j,  e_artif = e_w[j][c] - P_all;
+ *   energies are summed over the C channels and the W + F - 1 samples:
+ *     SDR = |s_true|^2 / |e_w - s_true|^2, ISR = |s_true|^2 / |e_spat|^2, SIR = |P_j|^2 / |e_interf|^2, SAR = |P_all|^2 / |e_artif|^2,
+ *   each 10 log10 of its quotient, +inf for a zero denominator.  A frame is NaN for EVERY source if some reference source, or some estimate, has
+ *   a channel sum sum_c x_w[i][c][t] of zero at every sample of the frame (museval's _any_source_silent; a stereo source with L = -R throughout a
+ *   frame counts as silent).  A track's score is the NaN-ignoring median over its frames, a corpus' the median over tracks.
+ *   sep_bss_image_energies  ref, est (B, n, C, T) fp32 rows of pitch T; filt_all (B, n, C, n C, flen): [b][j][c][k C + c2] = h_all[j][c][k][c2];
+ *                           filt_one (B, n, C, C, flen): [b][j][c][c2] = h_one[j][c][c2]; both fp64.  out (B, n, nwin, 9) fp64, per source j and
+ *                           frame w: |s_true|^2, |e_w - s_true|^2, |e_spat|^2, |P_j|^2, |e_interf|^2, |P_all|^2, |e_artif|^2, the count of frame
+ *                           samples whose reference channel sum is non-zero, the same count for the estimate (both sums formed in fp64).  The
+ *                           ratios, the silence rule and the medians are the caller's.  Frames at or beyond nwin_b are written as zeros.
+ *   sep_bss_image_scratch_bytes  72 B n nwin ceil((window + flen - 1) / 1024) bytes, 0 for arguments the call would refuse.  Not a launch: no
+ *                           stream, no sequence-table entry.  (The two sep_bss_xcorr calls before it need sep_bss_scratch_bytes(B, n C, n C, T, flen).)
+ * lengths, scratch, determinism: as the v3 calls -- T_b = lengths[b] clamped to [0, T], NULL means T; samples at and beyond T_b are never read; no
+ * atomics, a workgroup owns one slab of 1024 output samples counted from the FRAME's first sample, a second launch adds the slabs in ascending
+ * order: two runs give the same bits, and a row gives the same bits whatever the pitch T and the rows around it are.  The projected signals exist in
+ * registers only.  All offsets are 64-bit.  B <= 65535, n nwin <= 65535, n C <= 65535, T, flen, window and hop within 2^30. */
+size_t sep_bss_image_scratch_bytes(int B, int n, int C, int flen, int window, int nwin);
+int sep_bss_image_energies(const float* ref, const float* est, const double* filt_all, const double* filt_one, const int32_t* lengths, double* out,
+                           double* scratch, size_t scratch_bytes, int B, int n, int C, int T, int flen, int window, int hop, int nwin,
+                           sep_stream_t stream);
+
 /* ---- Mixture invariant training (MixIT, Wisdom et al. 2020; ABI 23, additive; csrc/loss.hip, criterion/mixit.py) ---------------------------------
  * M estimates est (B, M, T) of the sum of N reference mixtures tgt (B, N, T), fp32 rows of pitch T.  An assignment hands every estimate to exactly
  * one mixture; its code is sum_m n(m) N^(M-1-m) (itertools.product(range(N), repeat=M) order, estimate 0 most significant).  The remix of

@@ -1,0 +1,361 @@
+"""CPU: BSS-eval v4 ("images") -- utils/bss.py: bss_eval_images_batch / bss_eval_images / eval_track; csrc/loss.hip: sep_bss_image_energies;
+recipes/evaluate_musdb18.py.
+
+(a) the metric against the oracle of tests/test_bss_images_gpu.py (explicit delayed-reference matrix, numpy.linalg.lstsq, numpy.convolve per
+    frame; not the normal equations) at 1e-9 dB at the five shapes, on three routes: an emulator of the new call (ImagesEmu below, written from
+    its contract in include/sepkernels.h), the fp64 host composition that runs beside the HIP library without a GPU, and the kernel SOURCE on
+    the host (tools/hostsim.py).  The nine sums of the emulator and of the kernel source against the numpy restatement at 1e-12.
+(b) batch with lengths = the single calls bitwise, NaN beyond a row's frames; the three silent-frame cases; a perfect estimate; window > T; a
+    silent reference; an emulator with the filter sets exchanged or the frame origin shifted fails, so the comparison is not vacuous.
+(c) eval_track: the vocals / accompaniment rule and NaN-ignoring medians, against the oracle.
+(d) the library without a GPU: scratch size, argument checks before any launch, the sequence-table entry.
+(e) the function form of the MUSDB18 tester on a tiny random model, and the stand-alone sanitizer program.
+Without the feature `utils.bss` has no bss_eval_images and the binding no bss_image_energies: every test here fails."""
+import json
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import sepkernels
+import test_bss_images_gpu as TG
+from test_bss_eval_cpu import BssEmu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import hostsim                         # noqa: E402
+import hostsim_bss                     # noqa: E402
+import hostsim_bss_images              # noqa: E402
+
+needs_clang = pytest.mark.skipif(hostsim.compiler() is None, reason="needs clang++")
+
+
+class ImagesEmu(BssEmu):
+    """BssEmu plus sep_bss_image_energies from its contract, in fp64 torch on CPU tensors: sliding windows of the zero-padded frame segment"""
+
+    origin_shift = 0
+
+    def bss_image_scratch_bytes(self, B, n, C, flen, window, nwin):
+        return 72 * B * n * nwin * -(-(window + flen - 1) // 1024)
+
+    def bss_image_energies(self, ref, est, filt_all, filt_one, lengths, out, scratch, B, n, C, T, flen, window, hop, nwin):
+        out.zero_()
+        for b in range(B):
+            Tb = T if lengths is None else int(lengths[b])
+            for w in range(min(nwin, TG.num_frames(Tb, window, hop))):
+                o = w * hop + self.origin_shift
+                r, e = ref[b, :, :, o:o + window].double(), est[b, :, :, o:o + window].double()
+                win = torch.nn.functional.pad(r, (flen - 1, flen - 1)).unfold(-1, flen, 1).flip(-1)      # win[k][c2][t][tau] = r_w[k][c2][t - tau]
+                s, ex = (torch.nn.functional.pad(x, (0, flen - 1)) for x in (r, e))
+                p_all = torch.einsum("kdtx,jckdx->jct", win, filt_all[b].reshape(n, C, n, C, flen))
+                p_j = torch.einsum("jdtx,jcdx->jct", win, filt_one[b])
+                for q, v in enumerate((s, ex - s, p_j - s, p_j, p_all - p_j, p_all, ex - p_all)):
+                    out[b, :, w, q] = v.square().sum((1, 2))
+                out[b, :, w, 7] = (r.sum(1) != 0).sum(-1)
+                out[b, :, w, 8] = (e.sum(1) != 0).sum(-1)
+
+
+@pytest.fixture()
+def emu():
+    old = sepkernels._set_backend_for_tests(ImagesEmu())
+    try:
+        yield
+    finally:
+        sepkernels._set_backend_for_tests(old)
+
+
+@pytest.fixture()
+def native(monkeypatch):
+    monkeypatch.setenv("SEPK_BSS_EVAL", "native")
+    import utils.bss as bss
+    assert bss.__file__.startswith(os.path.join(ROOT, "dnn-based_source_separation_amd", "src"))
+    return bss
+
+
+@pytest.fixture()
+def emu_hooks():
+    saved = (TG.HIP, TG.to_device, TG.device_sync)
+    TG.HIP, TG.to_device, TG.device_sync = ImagesEmu(), (lambda t: t.clone()), (lambda: None)
+    try:
+        yield
+    finally:
+        TG.HIP, TG.to_device, TG.device_sync = saved
+
+
+# ------------------------------------------------------------------------------------------------------ (a) the metric, three routes
+@pytest.mark.parametrize("shape", TG.SHAPES, ids=TG.IDS)
+def test_metric_on_the_emulator_matches_the_definition(emu, native, shape):
+    TG.check_metric(native, "cpu", shape)
+    assert native.solve_route() == "host"
+
+
+@pytest.mark.parametrize("shape", TG.SHAPES, ids=TG.IDS)
+def test_metric_on_the_host_composition_matches_the_definition(native, shape):
+    """the product's own backend object: without a GPU that is the fp64 torch composition on the host"""
+    assert sepkernels.backend().name == "hip"
+    TG.check_metric(native, "cpu", shape)
+
+
+def test_a_backend_without_the_new_call_gets_the_host_composition(native):
+    old = sepkernels._set_backend_for_tests(BssEmu())
+    try:
+        assert not hasattr(sepkernels.backend(), "bss_image_energies")
+        TG.check_metric(native, "cpu", TG.SHAPES[0])
+    finally:
+        sepkernels._set_backend_for_tests(old)
+
+
+@pytest.mark.parametrize("shape", TG.SHAPES, ids=TG.IDS)
+def test_nine_sums_of_the_emulator(emu_hooks, shape):
+    TG.case_sums(*shape)
+
+
+def test_the_comparison_is_not_vacuous(emu_hooks):
+    """the filter sets exchanged (h_one in the place of source j's block of h_all and back), the frame origin shifted by one sample: both fail"""
+    class Swapped(ImagesEmu):
+        def bss_image_energies(self, ref, est, filt_all, filt_one, lengths, out, scratch, B, n, C, T, flen, *rest):
+            fa, fo = filt_all.reshape(B, n, C, n, C, flen).clone(), filt_one.clone()
+            for j in range(n):
+                fo[:, j], fa[:, j, :, j] = filt_all.reshape(B, n, C, n, C, flen)[:, j, :, j], filt_one[:, j]
+            return super().bss_image_energies(ref, est, fa.reshape(filt_all.shape), fo, lengths, out, scratch, B, n, C, T, flen, *rest)
+
+    class Shifted(ImagesEmu):
+        origin_shift = 1
+    for skewed in (Swapped(), Shifted()):
+        TG.HIP = skewed
+        with pytest.raises(AssertionError):
+            TG.case_sums(*TG.SHAPES[0], batch=False)
+    TG.HIP = ImagesEmu()
+    TG.case_sums(*TG.SHAPES[0], batch=False)
+
+
+# ------------------------------------------------------------------------------------------------------ (b) the rules around the metric
+def test_batch_with_lengths_equals_the_single_calls_bitwise(emu, native):
+    TG.check_batch_equals_single_calls(native, "cpu")
+
+
+def test_batch_on_the_host_composition_equals_the_single_calls_bitwise(native):
+    TG.check_batch_equals_single_calls(native, "cpu")
+
+
+def test_silent_frames(emu, native):
+    TG.check_silent_frames(native, "cpu")
+
+
+def test_silent_frames_on_the_host_composition(native):
+    TG.check_silent_frames(native, "cpu")
+
+
+def test_perfect_estimate_is_plus_infinity(emu, native):
+    ref, _ = TG.make_case(2, 2, 300, 8)
+    sdr, isr, sir, sar = native.bss_eval_images(ref, ref.clone(), 100, 100, filter_length=8)
+    assert (sdr == float("inf")).all() and sdr.shape == (2, 3)
+    assert not any(torch.isnan(v).any() for v in (isr, sir, sar)) and all((v > 100).all() for v in (isr, sir, sar))
+
+
+def test_window_longer_than_the_signal_gives_zero_frames(emu, native):
+    ref, est = TG.make_case(2, 2, 300, 8)
+    got = native.bss_eval_images_batch(ref[None], est[None], None, 301, 100, 8)
+    assert all(tuple(v.shape) == (1, 2, 0) and v.dtype == torch.float64 for v in got[:4]) and got[4].tolist() == [0]
+    got = native.bss_eval_images_batch(torch.stack([ref, ref]), torch.stack([est, est]), [300, 99], 100, 100, 8)
+    assert got[4].tolist() == [3, 0] and torch.isnan(got[0][1]).all() and torch.isfinite(got[0][0]).all()
+    assert all(tuple(v.shape) == (2, 0) for v in native.bss_eval_images(ref, est, 301, 301, filter_length=8))
+
+
+def test_silent_reference_is_a_value_error(emu, native):
+    ref, est = (x.clone() for x in TG.make_case(2, 2, 300, 8))
+    ref[1] = 0
+    with pytest.raises(ValueError, match="reference"):
+        native.bss_eval_images(ref, est, 100, 100, filter_length=8)
+    with pytest.raises(ValueError):
+        native.bss_eval_images_batch(ref[None], est[None, :, :1], None, 100, 100, 8)
+    with pytest.raises(ValueError):
+        native.bss_eval_images_batch(est[None], est[None], [301], 100, 100, 8)
+
+
+# ------------------------------------------------------------------------------------------------------ (c) eval_track
+def _stems():
+    n, C, T, F, W, H = TG.SHAPES[2]
+    ref, est = (x.clone() for x in TG.make_case(n, C, T, F))
+    est[2, :, W:2 * W] = 0                                             # a silent frame of the joint evaluation; the sum of the three stems is not silent
+    return ref, est, F, W, H
+
+
+def test_eval_track_takes_accompaniment_from_the_two_source_evaluation(emu, native):
+    ref, est, F, W, H = _stems()
+    names = ["bass", "drums", "other", "vocals"]
+    got = native.eval_track({k: ref[i] for i, k in enumerate(names)}, {k: est[i] for i, k in enumerate(names)}, rate=W, filter_length=F)
+    assert list(got) == names + ["accompaniment"]
+    joint = TG.oracle_arrays(ref.double().numpy(), est.double().numpy(), F, W, H)
+    # the accompaniment is the fp64 sum of the other stems rounded to the fp32 audio the kernels take
+    two = lambda x: np.stack([x[3], x[:3].sum(0).astype(np.float32).astype(np.float64)])       # noqa: E731
+    pair = TG.oracle_arrays(two(ref.double().numpy()), two(est.double().numpy()), F, W, H)
+    assert np.isnan(joint[:, :, 1]).all() and np.isfinite(joint[:, :, [0, 2, 3]]).all() and np.isfinite(pair).all()
+    for i, k in enumerate(names + ["accompaniment"]):
+        want = pair[:, 1] if k == "accompaniment" else joint[:, i]
+        TG.check_close([torch.tensor(got[k]["frames"][m], dtype=torch.float64) for m in native.IMAGE_METRICS], want, what="eval_track " + k)
+        for q, m in enumerate(native.IMAGE_METRICS):                   # the medians ignore the NaN frame
+            assert math.isfinite(got[k][m]) and got[k][m] == pytest.approx(np.nanmedian(want[q]), abs=1e-9)
+    assert not np.allclose(pair[:, 0], joint[:, 3], atol=1e-3), "the two evaluations differ for vocals: the rows must come from the joint one"
+    # without vocals there is one evaluation; a mono (T,) stem is a one-channel image
+    mono = native.eval_track({"a": ref[0, 0], "b": ref[1, 0]}, {"a": est[0, 0], "b": est[1, 0]}, rate=W, filter_length=F)
+    assert list(mono) == ["a", "b"] and len(mono["a"]["frames"]["SDR"]) == 4
+    with pytest.raises(ValueError):
+        native.eval_track({"vocals": ref[0]}, {"drums": est[0]}, rate=W)
+
+
+def test_nanmedian(native):
+    nan = float("nan")
+    assert native.nanmedian([3.0, nan, 1.0, 2.0]) == 2.0 and native.nanmedian([4.0, nan, 1.0, 2.0, 3.0]) == 2.5
+    assert math.isnan(native.nanmedian([nan, nan])) and math.isnan(native.nanmedian([]))
+    assert native.nanmedian([float("inf"), float("inf"), 1.0]) == float("inf")
+
+
+# ------------------------------------------------------------------------------------------------------ (d) the kernel source on the host
+@pytest.fixture(scope="module")
+def sim_library(tmp_path_factory):
+    return hostsim_bss.build_library(str(tmp_path_factory.mktemp("hostsim_bss_images")))
+
+
+@pytest.fixture()
+def on_host(sim_library):
+    saved = (TG.HIP, TG.to_device, TG.device_sync)
+    with hostsim.HostSimBackend(sim_library) as K:
+        TG.HIP, TG.to_device, TG.device_sync = K, (lambda t: t.clone()), (lambda: None)
+        try:
+            yield K
+        finally:
+            TG.HIP, TG.to_device, TG.device_sync = saved
+
+
+@needs_clang
+@pytest.mark.parametrize("shape", TG.SHAPES, ids=TG.IDS)
+def test_nine_sums_of_the_kernel_source_on_the_host(on_host, shape):
+    TG.case_sums(*shape)
+
+
+@needs_clang
+@pytest.mark.parametrize("shape", TG.SHAPES, ids=TG.IDS)
+def test_metric_through_the_kernel_source(on_host, native, shape):
+    class Named:
+        name = "hostsim"
+
+        def __getattr__(self, attr):
+            return getattr(on_host, attr)
+    old = sepkernels._set_backend_for_tests(Named())
+    try:
+        TG.check_metric(native, "cpu", shape)
+        if shape == TG.SHAPES[0]:
+            TG.check_batch_equals_single_calls(native, "cpu")
+            TG.check_silent_frames(native, "cpu")
+    finally:
+        sepkernels._set_backend_for_tests(old)
+
+
+@needs_clang
+def test_stand_alone_program_under_the_address_and_undefined_sanitizers():
+    """tools/hostsim/bss_images_main.cpp + the kernel source, built with -fsanitize=address,undefined into a program of its own and run: the
+    cases within 1e-12 of plain double loops on exactly-sized buffers, zero sanitizer reports"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "hostsim_bss_images.py"), "--asan"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "{} cases, 0 mismatches".format(hostsim_bss_images.CASES) in r.stdout and "sanitizer reports: 0" in r.stdout, r.stdout[-3000:]
+
+
+# ------------------------------------------------------------------------------------------------------ (d) the library without a GPU
+def test_scratch_size_and_sequence_entry_of_the_library():
+    lib = sepkernels.load()
+    for B, n, C, flen, W, nwin in [(1, 4, 2, 512, 44100, 240), (2, 2, 2, 8, 100, 3), (1, 3, 1, 16, 64, 5), (1, 2, 2, 64, 40, 15), (1, 2, 2, 512, 1500, 2)]:
+        want = 72 * B * n * nwin * -(-(W + flen - 1) // 1024)
+        assert lib.sep_bss_image_scratch_bytes(B, n, C, flen, W, nwin) == want == sepkernels.HipBackend().bss_image_scratch_bytes(B, n, C, flen, W, nwin)
+    assert lib.sep_bss_image_scratch_bytes(1, 2, 2, 0, 100, 3) == 0 and lib.sep_bss_image_scratch_bytes(1, 2, 2, 8, 100, 0) == 0
+    assert lib.sep_bss_image_scratch_bytes(1, 300, 2, 8, 100, 300) == 0
+    assert lib.sep_seq_lookup(b"sep_bss_image_scratch_bytes") == -1
+    k = lib.sep_seq_lookup(b"sep_bss_image_energies")
+    assert k >= 0 and lib.sep_seq_nargs(k) == 16 == len(sepkernels.SIGNATURES["sep_bss_image_energies"]) - 1
+    header = open(os.path.join(ROOT, "include", "sepkernels.h")).read()
+    assert "int sep_bss_image_energies(" in header and "size_t sep_bss_image_scratch_bytes(" in header
+
+
+def test_argument_checks_of_the_library_precede_the_launch():
+    """no launch happens here: each call fails its own checks before any HIP call (the pointers are never followed)"""
+    lib = sepkernels.load()
+    p, big = 1 << 12, 1 << 30
+    ok = (1, 2, 2, 300, 8, 100, 100, 3)                               # B, n, C, T, flen, window, hop, nwin
+    def args(**kw):                                                    # noqa: E306
+        v = dict(zip(("B", "n", "C", "T", "flen", "window", "hop", "nwin"), ok), **kw)
+        return tuple(v[k] for k in ("B", "n", "C", "T", "flen", "window", "hop", "nwin"))
+    for call, words in (((None, p, p, p, None, p, p, big) + ok, b"null pointer"), ((p, p, p, None, None, p, p, big) + ok, b"null pointer"),
+                        ((p, p, p, p, None, p, None, big) + ok, b"null pointer"),
+                        ((p, p, p, p, None, p, p, big) + args(flen=0), b"bad arguments"), ((p, p, p, p, None, p, p, big) + args(hop=0), b"bad arguments"),
+                        ((p, p, p, p, None, p, p, big) + args(C=0), b"bad arguments"), ((p, p, p, p, None, p, p, big) + args(nwin=0), b"bad arguments"),
+                        ((p, p, p, p, None, p, p, big) + args(T=0), b"bad arguments"), ((p, p, p, p, None, p, p, big) + args(window=-5), b"bad arguments"),
+                        ((p, p, p, p, None, p, p, big) + args(B=70000), b"grid limit"), ((p, p, p, p, None, p, p, big) + args(n=300, nwin=300), b"grid limit"),
+                        ((p, p, p, p, None, p, p, 72 * 2 * 3 - 1) + ok, b"scratch holds")):
+        assert lib.sep_bss_image_energies(*call, None) < 0
+        assert b"sep_bss_image_energies" in lib.sep_last_error() and words in lib.sep_last_error(), lib.sep_last_error()
+    with pytest.raises(sepkernels.SepKernelsError):                   # CPU tensors never reach a kernel
+        z = torch.zeros
+        sepkernels.HipBackend().bss_image_energies(z(1, 1, 1, 8), z(1, 1, 1, 8), z(1, 1, 1, 1, 2, dtype=torch.float64), z(1, 1, 1, 1, 2, dtype=torch.float64), None,
+                                                   z(1, 1, 2, 9, dtype=torch.float64), z(64, dtype=torch.float64), 1, 1, 1, 8, 2, 4, 4, 2)
+
+
+# ------------------------------------------------------------------------------------------------------ (e) the tester
+TINY = dict(n_basis=16, kernel_size=4, stride=2, enc_basis="trainable", dec_basis="trainable", enc_nonlinear=None, causal=False, sep_hidden_channels=32,
+            sep_bottleneck_channels=16, sep_skip_channels=16, sep_kernel_size=3, sep_num_blocks=1, sep_num_layers=2)
+
+
+@pytest.mark.parametrize("in_channels", [2, 1])
+def test_function_form_of_the_musdb18_tester(tmp_path, native, capsys, in_channels):
+    """a tiny random model, two synthetic 3-second stereo "tracks" at 400 Hz: frame lists of three one-second frames, medians, wav and json files,
+    and the scores equal to eval_track on the separation the tester ran"""
+    from models.conv_tasnet import ConvTasNet
+    from recipes import evaluate_musdb18 as ev
+    from recipes.audio_io import read_wav
+    rate, names = 400, ["bass", "drums", "other", "vocals"]
+    torch.manual_seed(3)
+    model = ConvTasNet(in_channels=in_channels, n_sources=4, **TINY)
+    g = torch.Generator().manual_seed(11)
+    tracks = []
+    for name in ("track one", "track two"):
+        stems = 0.1 * torch.randn(4, 2, 3 * rate + 57, generator=g)
+        tracks.append((name, stems.sum(0), {k: stems[i] for i, k in enumerate(names)}))
+    out = ev.evaluate_tracks(model, tracks, rate, names, window=rate, hop=rate // 2, batch_windows=3, out_dir=str(tmp_path), filter_length=16)
+    text = capsys.readouterr().out.splitlines()
+    assert len(text) == 3 and text[0].startswith("track one: bass SDR ") and text[2].startswith("median over 2 tracks: bass SDR ") and "accompaniment SDR" in text[2]
+    assert list(out["tracks"]) == ["track one", "track two"] and list(out["median"]) == names + ["accompaniment"]
+    for name, mixture, refs in tracks:
+        scores = out["tracks"][name]
+        est = ev.separate_track(model, mixture, rate, rate // 2, 3)
+        assert est.shape == (4, 2, 3 * rate + 57)
+        direct = native.eval_track(refs, {k: est[i] for i, k in enumerate(names)}, rate, filter_length=16)
+        saved = json.load(open(os.path.join(str(tmp_path), name + ".json")))
+        for k in names + ["accompaniment"]:
+            assert len(scores[k]["frames"]["SDR"]) == 3 and all(math.isfinite(scores[k][m]) for m in native.IMAGE_METRICS)
+            assert scores[k] == direct[k] == saved["targets"][k]
+        wav, sr = read_wav(os.path.join(str(tmp_path), name, "vocals.wav"))
+        assert sr == rate and wav.shape == (2, 3 * rate + 57) and torch.allclose(wav, est[3].clamp(-1, 1), atol=2.0 / 32768)
+    for k in out["median"]:
+        for m in native.IMAGE_METRICS:
+            assert out["median"][k][m] == pytest.approx(np.median([out["tracks"][t][k][m] for t in out["tracks"]]), abs=1e-12)
+
+
+def test_fixed_order_windows_cross_fade_to_the_model_output_of_a_linear_model():
+    """the cross-fade of the multichannel route: weights add to one, windows land where they were cut -- shown with a stand-in `model` that
+    scales its input per source, for which separation window by window equals separation of the whole"""
+    from recipes import evaluate_musdb18 as ev
+
+    class Scale(torch.nn.Module):
+        in_channels = 2
+
+        def forward(self, x):                                          # (B, 1, 2, T) -> (B, 3, 2, T)
+            return x * torch.tensor([1.0, -2.0, 0.5]).view(1, 3, 1, 1)
+    x = torch.randn(2, 1000, generator=torch.Generator().manual_seed(1))
+    for window, hop in ((256, 128), (300, 200), (2000, 1000)):
+        got = ev.separate_track(Scale(), x, window, hop, batch_windows=2)
+        assert got.shape == (3, 2, 1000) and torch.allclose(got, x[None] * torch.tensor([1.0, -2.0, 0.5]).view(3, 1, 1), atol=1e-6)
+    with pytest.raises(ValueError):
+        ev.separate_track(Scale(), x, 300, 100)
