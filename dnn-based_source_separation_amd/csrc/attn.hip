@@ -24,22 +24,10 @@ namespace {
 
 typedef float att_f32x16 __attribute__((ext_vector_type(16)));
 constexpr int ATT_MAXL = 320;          // (two sizes of every kernel: tiles for 256 and for 320 steps)
-
-__device__ __forceinline__ float4 ald4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 constexpr float ATT_LOG2E = 1.4426950408889634f, ATT_LN2 = 0.6931471805599453f;
 // the scores are kept in units of log 2 (q, or k, is scaled by scale * log2(e) on load): v_exp_f32 with nothing in front of it
 __device__ __forceinline__ float att_exp2(const float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ int att_row(const int r, const int lk) { return (r & 3) + 8 * (r >> 2) + 4 * lk; }      // row of result register r
-// idx: the element's 64-bit index ((n H + h) L + q) L + key -- beyond 2^32 probabilities (N H L^2) the high word enters the hash too, so the
-// mask does not repeat; below that it is zero and changes nothing
-__device__ __forceinline__ unsigned att_hash(const unsigned long long idx, const unsigned s0, const unsigned s1) {
-    unsigned x = (unsigned)idx ^ s0;
-    x *= 0x9E3779B1u; x ^= x >> 15;
-    x *= 0x85EBCA6Bu; x ^= x >> 13;
-    x += s1 + (unsigned)(idx >> 32) * 0x9E3779B1u;
-    x *= 0xC2B2AE35u; x ^= x >> 16;
-    return x;
-}
 struct att_args {
     const float* qkv;
     const float* o;
@@ -61,7 +49,7 @@ __device__ __forceinline__ void att_fill(float* tile, const float* src, const si
     for (int i = threadIdx.x; i < Lp * (D / 4); i += NT) {
         const int row = i / (D / 4), d4 = i % (D / 4);
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row < L) v = ald4(src + (size_t)row * row_stride + 4 * d4);
+        if (row < L) v = ld4(src + (size_t)row * row_stride + 4 * d4);
         *reinterpret_cast<float4*>(&tile[row * KLD + 4 * d4]) = v;
     }
 }
@@ -91,7 +79,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const att_args p) {
 #pragma unroll
     for (int j = 0; j < DH / 4; ++j) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q < L) v = ald4(base + (size_t)q * RS + lk * DH + 4 * j);
+        if (q < L) v = ld4(base + (size_t)q * RS + lk * DH + 4 * j);
         const float sc = p.scale * ATT_LOG2E;
         qv[4 * j] = v.x * sc; qv[4 * j + 1] = v.y * sc; qv[4 * j + 2] = v.z * sc; qv[4 * j + 3] = v.w * sc;
     }
@@ -107,7 +95,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const att_args p) {
         const float* kp = &Kr[(kb * 32 + l31) * KLD + lk * DH];
 #pragma unroll
         for (int j = 0; j < DH / 4; ++j) {
-            const float4 a = ald4(kp + 4 * j);
+            const float4 a = ld4(kp + 4 * j);
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, qv[4 * j], s, 0, 0, 0);
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, qv[4 * j + 1], s, 0, 0, 0);
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, qv[4 * j + 2], s, 0, 0, 0);
@@ -128,7 +116,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const att_args p) {
         for (int r = 0; r < 16; ++r) {
             float e = att_exp2(s[r] - mn);                   // 2^-inf = 0 for the dead keys
             ps += e;
-            if (p.thr != 0u) e = att_hash(ebase + (unsigned)(kb * 32 + att_row(r, lk)), p.s0, p.s1) >= p.thr ? e * p.keep_inv : 0.f;
+            if (p.thr != 0u) e = dropout_hash(ebase + (unsigned)(kb * 32 + att_row(r, lk)), p.s0, p.s1) >= p.thr ? e * p.keep_inv : 0.f;
             s[r] = e;
         }
         sum = fmaf(sum, alpha, ps);
@@ -177,9 +165,9 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const att_args p) {
     for (int j = 0; j < DH / 4; ++j) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f), g = v, oo = v;
         if (q < L) {
-            v = ald4(base + (size_t)q * RS + lk * DH + 4 * j);
-            g = ald4(p.dout + ((size_t)n * L + q) * OS + (size_t)h * D + lk * DH + 4 * j);
-            oo = ald4(p.o + ((size_t)n * L + q) * OS + (size_t)h * D + lk * DH + 4 * j);
+            v = ld4(base + (size_t)q * RS + lk * DH + 4 * j);
+            g = ld4(p.dout + ((size_t)n * L + q) * OS + (size_t)h * D + lk * DH + 4 * j);
+            oo = ld4(p.o + ((size_t)n * L + q) * OS + (size_t)h * D + lk * DH + 4 * j);
         }
         const float sc = p.scale * ATT_LOG2E;
         qv[4 * j] = v.x * sc; qv[4 * j + 1] = v.y * sc; qv[4 * j + 2] = v.z * sc; qv[4 * j + 3] = v.w * sc;
@@ -205,7 +193,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const att_args p) {
         const float* vp = &Vr[(kb * 32 + l31) * KLD + lk * DH];
 #pragma unroll
         for (int j = 0; j < DH / 4; ++j) {
-            const float4 a = ald4(kp + 4 * j), c = ald4(vp + 4 * j);
+            const float4 a = ld4(kp + 4 * j), c = ld4(vp + 4 * j);
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, qv[4 * j], s, 0, 0, 0);
             dp = __builtin_amdgcn_mfma_f32_32x32x2f32(c.x, dov[4 * j], dp, 0, 0, 0);
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, qv[4 * j + 1], s, 0, 0, 0);
@@ -220,7 +208,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_kernel(const att_args p) {
             const int key = kb * 32 + att_row(r, lk);
             const float pr = key < L ? att_exp2(s[r] - lse) : 0.f;
             float dpv = dp[r];
-            if (p.thr != 0u) dpv = att_hash(ebase + (unsigned)key, p.s0, p.s1) >= p.thr ? dpv * p.keep_inv : 0.f;
+            if (p.thr != 0u) dpv = dropout_hash(ebase + (unsigned)key, p.s0, p.s1) >= p.thr ? dpv * p.keep_inv : 0.f;
             s[r] = pr * (dpv - dl);                          // dS
         }
 #pragma unroll
@@ -265,8 +253,8 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kv_kernel(const att_args p) 
     for (int j = 0; j < DH / 4; ++j) {
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f), c = a;
         if (key < L) {
-            a = ald4(base + (size_t)key * RS + (size_t)H * D + lk * DH + 4 * j);
-            c = ald4(base + (size_t)key * RS + (size_t)2 * H * D + lk * DH + 4 * j);
+            a = ld4(base + (size_t)key * RS + (size_t)H * D + lk * DH + 4 * j);
+            c = ld4(base + (size_t)key * RS + (size_t)2 * H * D + lk * DH + 4 * j);
         }
         const float sc = p.scale * ATT_LOG2E;
         kv[4 * j] = a.x * sc; kv[4 * j + 1] = a.y * sc; kv[4 * j + 2] = a.z * sc; kv[4 * j + 3] = a.w * sc;
@@ -284,7 +272,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kv_kernel(const att_args p) 
         const float* gp = &Gr[(qb * 32 + l31) * KLD + lk * DH];
 #pragma unroll
         for (int j = 0; j < DH / 4; ++j) {
-            const float4 a = ald4(qp + 4 * j), c = ald4(gp + 4 * j);
+            const float4 a = ld4(qp + 4 * j), c = ld4(gp + 4 * j);
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, kv[4 * j], s, 0, 0, 0);
             dp = __builtin_amdgcn_mfma_f32_32x32x2f32(c.x, vv[4 * j], dp, 0, 0, 0);
             s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, kv[4 * j + 1], s, 0, 0, 0);
@@ -301,7 +289,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kv_kernel(const att_args p) 
             const float pr = live ? att_exp2(s[r] - lse_s[qq]) : 0.f;
             float pd = pr, dpv = dp[r];
             if (p.thr != 0u) {
-                const bool keep = att_hash((unsigned long long)(hbase + qq) * (unsigned long long)L + (unsigned)key, p.s0, p.s1) >= p.thr;
+                const bool keep = dropout_hash((unsigned long long)(hbase + qq) * (unsigned long long)L + (unsigned)key, p.s0, p.s1) >= p.thr;
                 pd = keep ? pr * p.keep_inv : 0.f;
                 dpv = keep ? dpv * p.keep_inv : 0.f;
             }

@@ -22,7 +22,7 @@
 // tap's shift modulo four is uniform over the launch, so the pick of four out of eight is a uniform switch), masks with selects (what
 // lies beyond T may be NaN) and stores 16 bytes.  One writer per output element, no atomics.
 //
-// One (b, c) row per workgroup, as the depthwise row kernels of stream.hip: the normalised row is formed ONCE into LDS (float4 loads of
+// One (b, c) row per workgroup, as the depthwise row kernels of depthwise.hip: the normalised row is formed ONCE into LDS (float4 loads of
 // a, mean, rstd), the taps then read LDS -- float4 where every tap shift is a multiple of four frames (d % 4 == 0), one frame per lane
 // (conflict-free) otherwise.  Any kernel width, any dilation >= 1, 0 <= pad <= (Kw - 1) d; three taps are unrolled.  Rows that do not
 // fit the LDS take the same kernels with the prologue evaluated per tap from global memory.  Plain loads and vector stores, no atomics:
@@ -31,9 +31,6 @@
 #include <stdlib.h>
 
 namespace {
-
-__device__ __forceinline__ float4 cd_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void cd_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 constexpr size_t CD_LDS_ROW_BYTES = 64 * 1024;      // the staged row: up to 16384 frames
 
@@ -57,7 +54,7 @@ __device__ __forceinline__ float cd_v1(const CdRow& r, const int i) {
 // the whole normalised row into LDS: frames [0, ldt), zeros from T on
 __device__ __forceinline__ void cd_stage_row(const CdRow& r, float* rowbuf, const int ldt) {
     for (int t = 4 * threadIdx.x; t < ldt; t += 1024) {
-        const float4 xv = cd_ld4(r.x + t), m4 = cd_ld4(r.mean + t), r4 = cd_ld4(r.rstd + t);
+        const float4 xv = ld4(r.x + t), m4 = ld4(r.mean + t), r4 = ld4(r.rstd + t);
         const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, ms[4] = {m4.x, m4.y, m4.z, m4.w}, rs[4] = {r4.x, r4.y, r4.z, r4.w};
         float o[4];
 #pragma unroll
@@ -65,7 +62,7 @@ __device__ __forceinline__ void cd_stage_row(const CdRow& r, float* rowbuf, cons
             const float u = r.act ? prelu_f(xs[e], r.al) : xs[e];
             o[e] = t + e < r.T ? (u - ms[e]) * rs[e] * r.ga + r.be : 0.f;
         }
-        cd_st4(rowbuf + t, make_float4(o[0], o[1], o[2], o[3]));
+        st4(rowbuf + t, make_float4(o[0], o[1], o[2], o[3]));
     }
 }
 
@@ -108,11 +105,11 @@ __global__ __launch_bounds__(256) void cd_depthwise_fwd_kernel(const float* __re
             for (int k = 0; k < Kw; ++k) {          // (Kw is a constant in the three-tap instance: unrolled)
                 const int i = t + k * dil - pad;
                 if (i < 0 || i >= ldt) continue;
-                const float4 v = cd_ld4(rowbuf + i);
+                const float4 v = ld4(rowbuf + i);
                 const float wk = wr[k];
                 o[0] = fmaf(wk, v.x, o[0]); o[1] = fmaf(wk, v.y, o[1]); o[2] = fmaf(wk, v.z, o[2]); o[3] = fmaf(wk, v.w, o[3]);
             }
-            cd_st4(yr + t, make_float4(t < T ? o[0] : 0.f, t + 1 < T ? o[1] : 0.f, t + 2 < T ? o[2] : 0.f, t + 3 < T ? o[3] : 0.f));
+            st4(yr + t, make_float4(t < T ? o[0] : 0.f, t + 1 < T ? o[1] : 0.f, t + 2 < T ? o[2] : 0.f, t + 3 < T ? o[3] : 0.f));
         }
         return;
     }
@@ -190,7 +187,7 @@ __global__ __launch_bounds__(256) void cd_sum_f64_kernel(const float* __restrict
 // frames [i, i + 4) of a row of ldt floats (ldt % 4 == 0), i of any sign and alignment, as aligned 16-byte loads; r = i & 3 is uniform over
 // the launch.  Quads that are not wholly inside [0, ldt) read as zero: their frames are outside [0, T) and masked by the caller anyway.
 __device__ __forceinline__ float4 ud_quad(const float* __restrict__ row, const int q, const int ldt) {
-    return (q >= 0 && q + 4 <= ldt) ? cd_ld4(row + q) : make_float4(0.f, 0.f, 0.f, 0.f);
+    return (q >= 0 && q + 4 <= ldt) ? ld4(row + q) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 __device__ __forceinline__ float4 ud_window(const float* __restrict__ row, const int i, const int ldt) {
     const int r = i & 3, q = i - r;
@@ -220,7 +217,7 @@ __global__ __launch_bounds__(256) void ud_unfold_kernel(const float* __restrict_
     float* cr = cols + (size_t)row * P * ldt + t;
     for (int p = 0; p < P; ++p) {
         const int i = t + p * dil - pad;
-        cd_st4(cr + (size_t)p * ldt, ud_mask(ud_window(xr, i, ldt), t, i, T));
+        st4(cr + (size_t)p * ldt, ud_mask(ud_window(xr, i, ldt), t, i, T));
     }
 }
 
@@ -236,7 +233,7 @@ __global__ __launch_bounds__(256) void ud_fold_kernel(const float* __restrict__ 
         const float4 v = ud_mask(ud_window(cr + (size_t)p * ldt, i, ldt), u, i, T);
         acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
     }
-    cd_st4(dx + (size_t)row * ldt + u, acc);
+    st4(dx + (size_t)row * ldt + u, acc);
 }
 
 inline bool cd_args_ok(int B, int C, int T, int ldt, int Kw, int pad, int dil) {

@@ -70,9 +70,56 @@ __device__ __forceinline__ T block_sum_n(T v, T* sm) {
     return r;
 }
 
+// The butterfly sum of LEN values per lane over the 64 lanes of a wave, as a reduce-scatter: while the count is even a step hands HALF of the
+// values to the partner lane and adds the partner's copies of the other half, so 80 values take 40 + 20 + 10 + 5 + 5 + 5 exchanges instead of
+// 6 x 80.  Every sum is formed from the same two operands, in the same order of steps (32, 16, ... 1), as `v += __shfl_xor(v, o)` forms it: the
+// bits are those of wave_sum.  On return acc[0 .. wave_fold_left(LEN)) of a lane hold the totals of the values base .. base + that many, in
+// every lane; lanes that differ only in the bits of wave_fold_shared(LEN) hold the same ones.  (A power of two LEN <= 64 halves down to ONE
+// value per lane, acc[0] = the total of value `base`: 63 exchanges for 64 values.)  Start with O = 32 and base = 0.
+constexpr int wave_fold_left(int len) {
+    for (int o = 32; o > 0 && len % 2 == 0; o >>= 1) len /= 2;
+    return len;
+}
+constexpr int wave_fold_shared(int len) {
+    int o = 32;
+    for (; o > 0 && len % 2 == 0; o >>= 1) len /= 2;
+    return o > 0 ? 2 * o - 1 : 0;  // the steps left once the count is odd are whole butterflies: their lane bits
+}
+template <int LEN, int O>
+__device__ __forceinline__ void wave_fold(double* acc, const int lane, int& base) {
+    if constexpr (O > 0 && LEN % 2 == 0) {
+        constexpr int H = LEN / 2;
+        const bool up = (lane & O) != 0;
+#pragma unroll
+        for (int q = 0; q < H; ++q) {
+            const double keep = up ? acc[q + H] : acc[q], send = up ? acc[q] : acc[q + H];
+            acc[q] = keep + __shfl_xor(send, O, 64);
+        }
+        if (up) base += H;
+        wave_fold<H, (O >> 1)>(acc, lane, base);
+    } else if constexpr (O > 0) {
+#pragma unroll
+        for (int q = 0; q < LEN; ++q) acc[q] += __shfl_xor(acc[q], O, 64);
+        wave_fold<LEN, (O >> 1)>(acc, lane, base);
+    }
+}
+
 // 16-byte access to four consecutive floats (p 16-byte aligned)
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+
+// The counter-based hash behind every dropout mask (attention probabilities, the row norms' residual branch): a mask is a FUNCTION of (seed,
+// element index), so a backward pass forms it again instead of reading a mask tensor.  idx: the element's 64-bit index; s0, s1: the 64-bit seed
+// as two words.  Beyond 2^32 elements the high word of idx enters the hash too, so the mask does not repeat; below that it is zero and changes
+// nothing.
+__device__ __forceinline__ unsigned dropout_hash(const unsigned long long idx, const unsigned s0, const unsigned s1) {
+    unsigned x = (unsigned)idx ^ s0;
+    x *= 0x9E3779B1u; x ^= x >> 15;
+    x *= 0x85EBCA6Bu; x ^= x >> 13;
+    x += s1 + (unsigned)(idx >> 32) * 0x9E3779B1u;
+    x *= 0xC2B2AE35u; x ^= x >> 16;
+    return x;
+}
 
 __device__ __forceinline__ float prelu_f(float x, float a) { return x > 0.f ? x : a * x; }
 __device__ __forceinline__ float prelu_grad(float x, float a) { return x > 0.f ? 1.f : a; }

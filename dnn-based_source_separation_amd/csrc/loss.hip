@@ -1120,43 +1120,10 @@ constexpr int ASSIGN_MAX_N = SEP_ASSIGN_MAX_N;  // one lane per column: the wave
 static_assert(PAIR_SLAB % 256 == 0, "a slab is a whole number of 256-sample steps");
 static_assert(ASSIGN_MAX_N == 64, "sep_assign gives every column a lane of one wavefront");
 
-// The butterfly sum of LEN values per lane over the 64 lanes of a wave, as a reduce-scatter: while the count is even a step hands HALF of the
-// values to the partner lane and adds the partner's copies of the other half, so 80 values take 40 + 20 + 10 + 5 + 5 + 5 exchanges instead of
-// 6 x 80.  Every sum is formed from the same two operands, in the same order of steps (32, 16, ... 1), as `v += __shfl_xor(v, o)` forms it: the
-// bits are those of wave_sum.  On return acc[0 .. pair_fold_left(LEN)) of a lane hold the totals of the values base .. base + that many, in
-// every lane; lanes that differ only in the bits of pair_fold_shared(LEN) hold the same ones.
-constexpr int pair_fold_left(int len) {
-    for (int o = 32; o > 0 && len % 2 == 0; o >>= 1) len /= 2;
-    return len;
-}
-constexpr int pair_fold_shared(int len) {
-    int o = 32;
-    for (; o > 0 && len % 2 == 0; o >>= 1) len /= 2;
-    return o > 0 ? 2 * o - 1 : 0;  // the steps left once the count is odd are whole butterflies: their lane bits
-}
-template <int LEN, int O>
-__device__ __forceinline__ void pair_wave_fold(double* acc, const int lane, int& base) {
-    if constexpr (O > 0 && LEN % 2 == 0) {
-        constexpr int H = LEN / 2;
-        const bool up = (lane & O) != 0;
-#pragma unroll
-        for (int q = 0; q < H; ++q) {
-            const double keep = up ? acc[q + H] : acc[q], send = up ? acc[q] : acc[q + H];
-            acc[q] = keep + __shfl_xor(send, O, 64);
-        }
-        if (up) base += H;
-        pair_wave_fold<H, (O >> 1)>(acc, lane, base);
-    } else if constexpr (O > 0) {
-#pragma unroll
-        for (int q = 0; q < LEN; ++q) acc[q] += __shfl_xor(acc[q], O, 64);
-        pair_wave_fold<LEN, (O >> 1)>(acc, lane, base);
-    }
-}
-
 // part[b][slab][.] = the slab's share of dots (n n values, [i][j]), then of tt (n), then of xx (n).  grid (nslab, blocks of i x blocks of j, B).
 // The workgroup owns estimates [RB bi, RB bi + RB) x targets [RB bj, RB bj + RB) as RB RB products in fp64 registers; the workgroups of the
 // first block column also hold |est_i|^2, those of the first block row |tgt_j|^2.  Rows beyond n enter as zeros and are not stored.  Per
-// thread the samples are added in ascending order, the wave by a butterfly (pair_wave_fold), the four waves in order.
+// thread the samples are added in ascending order, the wave by a butterfly (wave_fold, common.hpp), the four waves in order.
 template <int RB>
 __global__ __launch_bounds__(256) void pair_gram_kernel(const float* __restrict__ est, const float* __restrict__ tgt, double* __restrict__ part,
                                                         const int n, const int T, const int nslab) {
@@ -1201,8 +1168,8 @@ __global__ __launch_bounds__(256) void pair_gram_kernel(const float* __restrict_
         }
     }
     int base = 0;
-    pair_wave_fold<NACC, 32>(acc, lane, base);
-    constexpr int LEFT = pair_fold_left(NACC), SHARED = pair_fold_shared(NACC);
+    wave_fold<NACC, 32>(acc, lane, base);
+    constexpr int LEFT = wave_fold_left(NACC), SHARED = wave_fold_shared(NACC);
     if ((lane & SHARED) == 0) {
 #pragma unroll
         for (int q = 0; q < LEFT; ++q) red[w][base + q] = acc[q];
@@ -1450,17 +1417,3 @@ extern "C" int sep_pair_bwd(const float* est, const float* tgt, const double* do
     SEP_CHECK_LAUNCH("sep_pair_bwd");
     return 0;
 }
-
-// ---- error plumbing ---------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-void sep_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-extern "C" const char* sep_last_error(void) { return g_err; }
-static thread_local const char* g_kernel = "";
-void sep_set_kernel(const char* name) { g_kernel = name; }
-extern "C" const char* sep_last_kernel(void) { return g_kernel; }
-extern "C" int sep_version(void) { return SEP_ABI_VERSION; }

@@ -23,8 +23,6 @@ __device__ __forceinline__ float tanh_f(float x) {
     // tanh(x) = 1 - 2 / (1 + e^{2x}); exp2 overflow -> inf -> rcp 0 -> 1, underflow -> 0 -> -1
     return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(2.8853900817779268f * x));
 }
-__device__ __forceinline__ float4 ld4g(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4g(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 constexpr int LSTM_NS = 16;     // sequences per workgroup = N of the 16x16x4 MFMA
 
@@ -66,7 +64,7 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_kernel(const float* __restrict
     auto load_x = [&](int t, float4 (&dst)[4]) {
         const float* p = xg + (seq_base + t) * 4 * H + u0;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) dst[g] = ld4g(p + g * H);
+        for (int g = 0; g < 4; ++g) dst[g] = ld4(p + g * H);
     };
     float4 xc[4], xn[4];
     load_x(reverse ? L - 1 : 0, xc);
@@ -99,15 +97,15 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_kernel(const float* __restrict
         }
         if (live) {
             const size_t o = seq_base + t;
-            st4g(hout + o * hrow + u0, make_float4(hn[0], hn[1], hn[2], hn[3]));
+            st4(hout + o * hrow + u0, make_float4(hn[0], hn[1], hn[2], hn[3]));
             if (gates) {
                 float* gp = gates + o * 4 * H + u0;
-                st4g(gp, make_float4(gi[0], gi[1], gi[2], gi[3]));
-                st4g(gp + H, make_float4(gf[0], gf[1], gf[2], gf[3]));
-                st4g(gp + 2 * H, make_float4(gg[0], gg[1], gg[2], gg[3]));
-                st4g(gp + 3 * H, make_float4(go[0], go[1], go[2], go[3]));
+                st4(gp, make_float4(gi[0], gi[1], gi[2], gi[3]));
+                st4(gp + H, make_float4(gf[0], gf[1], gf[2], gf[3]));
+                st4(gp + 2 * H, make_float4(gg[0], gg[1], gg[2], gg[3]));
+                st4(gp + 3 * H, make_float4(go[0], go[1], go[2], go[3]));
             }
-            if (cstate) st4g(cstate + o * H + u0, make_float4(c[0], c[1], c[2], c[3]));
+            if (cstate) st4(cstate + o * H + u0, make_float4(c[0], c[1], c[2], c[3]));
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) xc[g] = xn[g];
@@ -149,11 +147,11 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_kernel(const float* __restrict
         const int tprev = reverse ? t + 1 : t - 1;                 // the step that fed c_{t-1}
         const bool has_prev = tprev >= 0 && tprev < L;
         const size_t o = seq_base + t;
-        const float4 dho = ld4g(dhout + o * hrow + u0);
+        const float4 dho = ld4(dhout + o * hrow + u0);
         const float* gp = gates + o * 4 * H + u0;
-        const float4 vi = ld4g(gp), vf = ld4g(gp + H), vg = ld4g(gp + 2 * H), vo = ld4g(gp + 3 * H);
-        const float4 vc = ld4g(cstate + o * H + u0);
-        const float4 vcp = has_prev ? ld4g(cstate + (seq_base + tprev) * H + u0) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 vi = ld4(gp), vf = ld4(gp + H), vg = ld4(gp + 2 * H), vo = ld4(gp + 3 * H);
+        const float4 vc = ld4(cstate + o * H + u0);
+        const float4 vcp = has_prev ? ld4(cstate + (seq_base + tprev) * H + u0) : make_float4(0.f, 0.f, 0.f, 0.f);
         const float dh4[4] = {dho.x, dho.y, dho.z, dho.w};
         const float gi[4] = {vi.x, vi.y, vi.z, vi.w}, gf[4] = {vf.x, vf.y, vf.z, vf.w};
         const float gg[4] = {vg.x, vg.y, vg.z, vg.w}, go[4] = {vo.x, vo.y, vo.z, vo.w};
@@ -176,10 +174,10 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_kernel(const float* __restrict
         }
         if (live) {
             float* dp = dxg + o * 4 * H + u0;
-            st4g(dp, make_float4(dai[0], dai[1], dai[2], dai[3]));
-            st4g(dp + H, make_float4(daf[0], daf[1], daf[2], daf[3]));
-            st4g(dp + 2 * H, make_float4(dag[0], dag[1], dag[2], dag[3]));
-            st4g(dp + 3 * H, make_float4(dao[0], dao[1], dao[2], dao[3]));
+            st4(dp, make_float4(dai[0], dai[1], dai[2], dai[3]));
+            st4(dp + H, make_float4(daf[0], daf[1], daf[2], daf[3]));
+            st4(dp + 2 * H, make_float4(dag[0], dag[1], dag[2], dag[3]));
+            st4(dp + 3 * H, make_float4(dao[0], dao[1], dao[2], dao[3]));
         }
         __syncthreads();
         // dh_{t-1} += W_hh^T da_t   (this wave: its 16 hidden units x 16 sequences)
@@ -238,7 +236,7 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd4_kernel(const float* __restric
         const float* wr = whh + (size_t)(hi * H + u) * H;
 #pragma unroll
         for (int k = 0; k < H; k += 4) {
-            const float4 v = ld4g(wr + k);
+            const float4 v = ld4(wr + k);
             wf[k] = v.x; wf[k + 1] = v.y; wf[k + 2] = v.z; wf[k + 3] = v.w;
         }
     }

@@ -8,25 +8,12 @@
 //   forward : s = x + drop(r) ; y = (s - mu) rstd gamma + beta ; stat[row] = {mu, rstd}                         reads x, r ; writes s, y
 //   backward: ds = rstd (g gamma - mean(g gamma) - xhat mean(g gamma xhat)) ; dr = drop'(ds)                    reads dy, s ; writes ds [, dr]
 //             part[w] = {sum_rows dy xhat [C] | sum_rows dy [C]} of the rows workgroup w took
-// drop() is the inverted dropout of nn.Dropout with a mask that is a FUNCTION of (seed, element index) -- the hash of csrc/attn.hip -- so the
+// drop() is the inverted dropout of nn.Dropout with a mask that is a FUNCTION of (seed, element index) -- dropout_hash of common.hpp -- so the
 // backward pass forms it again instead of reading a mask tensor.  One wave per row (64 lanes x float4 x NJ trips, C <= 1024), rows strided over
 // the grid's waves; mean and variance in two passes over the REGISTERS (no E[x^2] - E[x]^2).  HBM-bound: 4 rows of C floats each way.
 #include "common.hpp"
 
 namespace {
-
-__device__ __forceinline__ float4 rn_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void rn_st4(float* p, const float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-// the mixing of att_hash (csrc/attn.hip): 64-bit element index, 64-bit seed as two words
-__device__ __forceinline__ unsigned rn_hash(const unsigned long long idx, const unsigned s0, const unsigned s1) {
-    unsigned x = (unsigned)idx ^ s0;
-    x *= 0x9E3779B1u; x ^= x >> 15;
-    x *= 0x85EBCA6Bu; x ^= x >> 13;
-    x += s1 + (unsigned)(idx >> 32) * 0x9E3779B1u;
-    x *= 0xC2B2AE35u; x ^= x >> 16;
-    return x;
-}
 
 struct rn_drop {
     unsigned thr, s0, s1;       // thr == 0: no dropout
@@ -54,8 +41,8 @@ __global__ __launch_bounds__(256) void rownorm_fwd_kernel(const float* __restric
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int c = 4 * lane + 256 * j;
-        g4[j] = c < C ? rn_ld4(gamma + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        b4[j] = c < C ? rn_ld4(beta + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        g4[j] = c < C ? ld4(gamma + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        b4[j] = c < C ? ld4(beta + c) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     const float inv_c = 1.f / (float)C;
     for (long row = (long)blockIdx.x * 4 + w; row < rows; row += (long)gridDim.x * 4) {
@@ -67,16 +54,16 @@ __global__ __launch_bounds__(256) void rownorm_fwd_kernel(const float* __restric
             const int c = 4 * lane + 256 * j;
             float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
             if (c < C) {
-                a = rn_ld4(x + base + c);
+                a = ld4(x + base + c);
                 if (r) {
-                    const float4 q = rn_ld4(r + base + c);
+                    const float4 q = ld4(r + base + c);
                     float qv[4] = {q.x, q.y, q.z, q.w};
                     if (dr.thr != 0u) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) qv[e] = rn_hash((unsigned long long)(base + c + e), dr.s0, dr.s1) >= dr.thr ? qv[e] * dr.keep_inv : 0.f;
+                        for (int e = 0; e < 4; ++e) qv[e] = dropout_hash((unsigned long long)(base + c + e), dr.s0, dr.s1) >= dr.thr ? qv[e] * dr.keep_inv : 0.f;
                     }
                     a.x += qv[0]; a.y += qv[1]; a.z += qv[2]; a.w += qv[3];
-                    if (s_out) rn_st4(s_out + base + c, a);
+                    if (s_out) st4(s_out + base + c, a);
                 }
             }
             v[j][0] = a.x; v[j][1] = a.y; v[j][2] = a.z; v[j][3] = a.w;
@@ -97,7 +84,7 @@ __global__ __launch_bounds__(256) void rownorm_fwd_kernel(const float* __restric
         for (int j = 0; j < NJ; ++j) {
             const int c = 4 * lane + 256 * j;
             if (c < C)
-                rn_st4(y + base + c, make_float4(fmaf((v[j][0] - mu) * rstd, g4[j].x, b4[j].x), fmaf((v[j][1] - mu) * rstd, g4[j].y, b4[j].y),
+                st4(y + base + c, make_float4(fmaf((v[j][0] - mu) * rstd, g4[j].x, b4[j].x), fmaf((v[j][1] - mu) * rstd, g4[j].y, b4[j].y),
                                                  fmaf((v[j][2] - mu) * rstd, g4[j].z, b4[j].z), fmaf((v[j][3] - mu) * rstd, g4[j].w, b4[j].w)));
         }
     }
@@ -113,7 +100,7 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const float* __restric
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int c = 4 * lane + 256 * j;
-        const float4 g4 = c < C ? rn_ld4(gamma + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 g4 = c < C ? ld4(gamma + c) : make_float4(0.f, 0.f, 0.f, 0.f);
         ga[j][0] = g4.x; ga[j][1] = g4.y; ga[j][2] = g4.z; ga[j][3] = g4.w;
 #pragma unroll
         for (int e = 0; e < 4; ++e) { pg[j][e] = 0.f; pb[j][e] = 0.f; }
@@ -128,7 +115,7 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const float* __restric
         for (int j = 0; j < NJ; ++j) {
             const int c = 4 * lane + 256 * j;
             float4 g = make_float4(0.f, 0.f, 0.f, 0.f), v = make_float4(mu, mu, mu, mu);
-            if (c < C) { g = rn_ld4(dy + base + c); v = rn_ld4(s + base + c); }
+            if (c < C) { g = ld4(dy + base + c); v = ld4(s + base + c); }
             const float gv[4] = {g.x, g.y, g.z, g.w}, sv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -148,11 +135,11 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const float* __restric
                 float o[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = rstd * (gg[j][e] - m1 - xh[j][e] * m2);
-                rn_st4(ds + base + c, make_float4(o[0], o[1], o[2], o[3]));
+                st4(ds + base + c, make_float4(o[0], o[1], o[2], o[3]));
                 if (dres) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = rn_hash((unsigned long long)(base + c + e), dr.s0, dr.s1) >= dr.thr ? o[e] * dr.keep_inv : 0.f;
-                    rn_st4(dres + base + c, make_float4(o[0], o[1], o[2], o[3]));
+                    for (int e = 0; e < 4; ++e) o[e] = dropout_hash((unsigned long long)(base + c + e), dr.s0, dr.s1) >= dr.thr ? o[e] * dr.keep_inv : 0.f;
+                    st4(dres + base + c, make_float4(o[0], o[1], o[2], o[3]));
                 }
             }
         }
@@ -178,22 +165,22 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const float* __restric
 // gradient is: dh = a != 0 ? dy / (1 - p) : 0 (a is saved by the product that consumes it anyway).  Two streams forward, three backward.
 __global__ __launch_bounds__(256) void relu_drop_fwd_kernel(const float* __restrict__ h, float* __restrict__ a, long n4, rn_drop dr) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const float4 v = rn_ld4(h + 4 * i);
+        const float4 v = ld4(h + 4 * i);
         float o[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const bool keep = dr.thr == 0u || rn_hash((unsigned long long)(4 * i + e), dr.s0, dr.s1) >= dr.thr;
+            const bool keep = dr.thr == 0u || dropout_hash((unsigned long long)(4 * i + e), dr.s0, dr.s1) >= dr.thr;
             o[e] = (o[e] > 0.f && keep) ? o[e] * dr.keep_inv : 0.f;
         }
-        rn_st4(a + 4 * i, make_float4(o[0], o[1], o[2], o[3]));
+        st4(a + 4 * i, make_float4(o[0], o[1], o[2], o[3]));
     }
 }
 
 __global__ __launch_bounds__(256) void relu_drop_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ a, float* __restrict__ dh, long n4,
                                                             float keep_inv) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const float4 g = rn_ld4(dy + 4 * i), v = rn_ld4(a + 4 * i);
-        rn_st4(dh + 4 * i, make_float4(v.x != 0.f ? g.x * keep_inv : 0.f, v.y != 0.f ? g.y * keep_inv : 0.f, v.z != 0.f ? g.z * keep_inv : 0.f,
+        const float4 g = ld4(dy + 4 * i), v = ld4(a + 4 * i);
+        st4(dh + 4 * i, make_float4(v.x != 0.f ? g.x * keep_inv : 0.f, v.y != 0.f ? g.y * keep_inv : 0.f, v.z != 0.f ? g.z * keep_inv : 0.f,
                                        v.w != 0.f ? g.w * keep_inv : 0.f));
     }
 }

@@ -16,32 +16,10 @@ constexpr int STITCH_MAX_N = SEP_ASSIGN_MAX_N;      // the matching is sep_assig
 constexpr int CHAIN_BLOCK = 64;                     // windows of perm_local staged in LDS at a time: 64 x 64 ints, 16 KB
 static_assert(STITCH_MAX_N == SEP_WAVE, "sep_stitch_chain gives every track a lane of one wavefront");
 
-// The butterfly sum over the 64 lanes of a wave of LEN = 2^k values per lane as a reduce-scatter, the scheme of pair_wave_fold in csrc/loss.hip
-// for a power of two: while more than one value is left a step hands half of them to the partner lane and adds the partner's copies of the
-// other half (63 exchanges for 64 values instead of 6 x 64); the steps left after that are whole butterflies.  On return acc[0] is the total of
-// value `base`, in every lane that agrees with this one in the lane bits of the halving steps.
-template <int LEN, int O>
-__device__ __forceinline__ void stitch_wave_fold(double* acc, const int lane, int& base) {
-    if constexpr (O > 0 && LEN > 1) {
-        constexpr int H = LEN / 2;
-        const bool up = (lane & O) != 0;
-#pragma unroll
-        for (int q = 0; q < H; ++q) {
-            const double keep = up ? acc[q + H] : acc[q], send = up ? acc[q] : acc[q + H];
-            acc[q] = keep + __shfl_xor(send, O, 64);
-        }
-        if (up) base += H;
-        stitch_wave_fold<H, (O >> 1)>(acc, lane, base);
-    } else if constexpr (O > 0) {
-        acc[0] += __shfl_xor(acc[0], O, 64);
-        stitch_wave_fold<1, (O >> 1)>(acc, lane, base);
-    }
-}
-
 // cost[b][w][i][j] = sum_{t < O} (est[b][w][i][hop + t] - est[b][w + 1][j][t])^2.  grid (B (W - 1) boundaries, tiles of i x tiles of j): ONE
 // workgroup walks the whole overlap of its boundary with an RB x RB tile of pairs in fp64 registers, as pair_gram_kernel holds its products: a
 // sample is read ceil(n / RB) times per side, there is no scratch buffer and no second launch.  Per thread the samples are added in ascending
-// order, the wave by the butterfly above, the four waves in order: no atomics, the same bits every time.  A recording has W - 1 boundaries: a
+// order, the wave by the butterfly wave_fold (common.hpp), the four waves in order: no atomics, the same bits every time.  A recording has W - 1 boundaries: a
 // ten-minute one at 2 s hops launches 299 x ceil(n / 8)^2 workgroups that each walk 16000 samples -- latency-bound by design, and left so: the
 // stage stands beside W forwards of the model, which dominate it by orders of magnitude; a slab split over the overlap would
 // buy back microseconds at the price of a scratch buffer and a reduction launch.
@@ -108,7 +86,7 @@ __global__ __launch_bounds__(256) void stitch_cost_kernel(const float* __restric
         }
     }
     int base = 0;
-    stitch_wave_fold<NACC, 32>(acc, lane, base);
+    wave_fold<NACC, 32>(acc, lane, base);
     constexpr int SHARED = NACC >= 64 ? 0 : 64 / NACC - 1;   // lanes that differ only in these bits hold the same total: one of them stores it
     if ((lane & SHARED) == 0) red[wv][base] = acc[0];
     __syncthreads();

@@ -491,7 +491,7 @@ def depthwise_backward(dy, x, weight, dilation, left, has_bias, dweight=None, db
 class PaddedDepthwiseFn(torch.autograd.Function):
     """nn.Conv1d(C, C, k, dilation=d, groups=C) of a TCN layer on rows that carry the workspace stride, with the layer's zero padding folded
     in: `left` zeros in front (causal: (k - 1) d, all of it; else the smaller half -- reference tdcn.py:118-129), the output has the input's
-    n_frames.  x (B, C, ldt) with frames >= n_frames zero -> (B, C, ldt); sep_depthwise_* (csrc/stream.hip) on rows of ldt frames -- what
+    n_frames.  x (B, C, ldt) with frames >= n_frames zero -> (B, C, ldt); sep_depthwise_* (csrc/depthwise.hip) on rows of ldt frames -- what
     the kernel writes beyond n_frames is whatever the taps reach there and is ignored by every consumer (they all take n_frames)."""
 
     @staticmethod

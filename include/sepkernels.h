@@ -48,7 +48,7 @@ const char* sep_last_error(void);
  *   direct_rt<trans_a,prologue,two-source>         the same kernel with the epilogue flags read at run time
  *   staged                                         register-staged fallback
  *   wgrad_pc16<..> / wgrad_pc16_pre<..> / wgrad_pc16_batch<..> / wgrad_pc<..> / wgrad_split<..> / wgrad_direct<..> / wgrad
- * e.g. "pc<4,1,SEP_PRO_GLN_PRELU,false,SEP_EPI_RESIDUAL>".  The streaming dispatchers (csrc/stream.hip, cln.hip, causal.hip) name the kernel
+ * e.g. "pc<4,1,SEP_PRO_GLN_PRELU,false,SEP_EPI_RESIDUAL>".  The streaming dispatchers (csrc/filterbank.hip, tcn.hip, gln.hip, depthwise.hip, cln.hip, causal.hip) name the kernel
  * function and its template arguments as spelled at the launch; a run-time value that selects behaviour without a template argument
  * follows a "/":
  *   sep_encoder_fwd                   encoder_l16s8 | encoder<16> | encoder<0>

@@ -1,5 +1,5 @@
-"""Helper module (not a test file): the ledger of the kernel instances behind the streaming (non-GEMM) entry points of csrc/stream.hip,
-csrc/cln.hip and csrc/causal.hip, a case matrix that reaches every one of them BY NAME (sep_last_kernel), a float64 restatement of every
+"""Helper module (not a test file): the ledger of the kernel instances behind the streaming (non-GEMM) entry points of csrc/filterbank.hip,
+csrc/tcn.hip, csrc/gln.hip, csrc/depthwise.hip, csrc/cln.hip and csrc/causal.hip, a case matrix that reaches every one of them BY NAME (sep_last_kernel), a float64 restatement of every
 call's contract, and a metric local enough that one wrong row or one wrong halo frame cannot hide.  tests/test_stream_instances_cpu.py runs
 the matrix on the host simulation of the kernel sources, tests/test_stream_instances_gpu.py on the MI355X; the children of the latter start
 

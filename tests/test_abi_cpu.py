@@ -36,6 +36,34 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert sepkernels.STATS_SLOTS == 16
 
 
+def test_translation_units_are_listed_once_and_shared_helpers_defined_once():
+    """the build and the host simulation compile the same set of files, which is csrc/*.hip; every entry point of the header is defined in
+    exactly one of them; runtime.hip holds the five runtime functions and nothing else; the 16-byte load / store, the dropout hash and the
+    wave fold exist in common.hpp alone (a copy under another name would be found here)"""
+    for p in (ROOT, os.path.join(ROOT, "tools")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import __graft_entry__ as entry
+    import hostsim
+    csrc = os.path.join(ROOT, "dnn-based_source_separation_amd", "csrc")
+    on_disk = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert sorted(entry.HIP_SOURCES) == sorted(f + ".hip" for f in hostsim.FILES) == on_disk
+    assert len(on_disk) == len(set(entry.HIP_SOURCES)) == len(entry.HIP_SOURCES) == len(hostsim.FILES) >= 21
+    texts = {f: open(os.path.join(csrc, f)).read() for f in on_disk + ["common.hpp"]}
+    defined = {f: re.findall(r'^extern "C" [\w\s\*]*?\b(sep_[a-z0-9_]+)\s*\([^;{]*\)\s*\{', t, flags=re.M) for f, t in texts.items()}
+    homes = {n: [f for f, names in defined.items() for m in names if m == n] for n in _declared()}
+    assert all(len(h) == 1 for h in homes.values()), {n: h for n, h in homes.items() if len(h) != 1}
+    assert defined["runtime.hip"] == ["sep_last_error", "sep_last_kernel", "sep_version"]
+    assert re.findall(r"^(?:extern \"C\" )?[\w\s\*]*?\b(\w+)\s*\([^;{]*\)\s*\{", texts["runtime.hip"], flags=re.M) == [
+        "sep_set_error", "sep_last_error", "sep_set_kernel", "sep_last_kernel", "sep_version"]
+    once = {r"\{\s*return \*reinterpret_cast<const float4\*>\(\w+\);\s*\}": 1,          # a one-line float4 load helper
+            r"\{\s*\*reinterpret_cast<float4\*>\(\w+\) = \w+;\s*\}": 1,                  # ... and store
+            r"0x85EBCA6Bu": 1,                                                           # the dropout hash's second multiplier
+            r"void \w*wave_fold\(": 1}                                                   # a wave reduce-scatter template
+    for pattern, n in once.items():
+        assert {f: len(re.findall(pattern, t)) for f, t in texts.items() if re.search(pattern, t)} == {"common.hpp": n}, pattern
+
+
 def test_descriptor_layouts_match_the_header():
     # both: 12 int32 + float (+4 pad), double at offset 56, then pointers: the layouts the header's field order implies on LP64
     assert sepkernels.GemmDesc.arith.offset == 44 and sepkernels.GemmDesc.eps.offset == 48

@@ -88,7 +88,7 @@ def test_the_split_arithmetic_and_the_block_decode_are_spelled_in_one_file():
     changes behind the helper -- exactly two occurrences there, so a third copy is still found"""
     csrc = os.path.join(ROOT, "dnn-based_source_separation_amd", "csrc")
     texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if os.path.isfile(os.path.join(csrc, f))}
-    assert {"common.hpp", "gemm_common.hpp", "gemm.hip", "gemm_coop.hip", "gemm_pc.hip", "wgrad_pc.hip", "wgrad_pc16.hip", "stream.hip", "cln.hip"} <= set(texts)
+    assert {"common.hpp", "gemm_common.hpp", "gemm.hip", "gemm_coop.hip", "gemm_pc.hip", "wgrad_pc.hip", "wgrad_pc16.hip", "filterbank.hip", "tcn.hip", "gln.hip", "depthwise.hip", "cln.hip"} <= set(texts)
     once = {"v_fma_mix_f32": "gemm_common.hpp",
             "__builtin_amdgcn_mfma_f32_32x32x16_f16(": "gemm_common.hpp",
             "__builtin_amdgcn_mfma_f32_32x32x16_bf16(": "gemm_common.hpp",

@@ -1,7 +1,8 @@
-"""CPU: every kernel instance behind the streaming entry points of csrc/stream.hip, csrc/cln.hip and csrc/causal.hip, reached BY NAME on the
-host simulation of the kernel sources and compared with a float64 restatement of the call's contract, row by row and sum by sum
-(tests/stream_matrix.py: the ledger, the case matrix, the reference, the metric and the measured bounds).  The default environment runs in
-this process, family by family; each A/B switch in a child process -- the dispatchers read their SEPK_* switches once per process."""
+"""CPU: every kernel instance behind the streaming entry points of csrc/filterbank.hip, csrc/tcn.hip, csrc/gln.hip, csrc/depthwise.hip,
+csrc/cln.hip and csrc/causal.hip, reached BY NAME on the host simulation of the kernel sources and compared with a float64 restatement of
+the call's contract, row by row and sum by sum (tests/stream_matrix.py: the ledger, the case matrix, the reference, the metric and the
+measured bounds).  The default environment runs in this process, family by family; each A/B switch in a child process -- the dispatchers
+read their SEPK_* switches once per process."""
 import json
 import os
 import re
@@ -74,7 +75,7 @@ def test_under_a_switch_every_case_reaches_the_forced_instance(sim_library, tmp_
 
 
 def test_the_ledger_lists_every_launch_line_of_the_dispatchers():
-    """INSTANCES against the sources: every sep_set_kernel statement of the three files, a statement inside a launch macro counted once per use
+    """INSTANCES against the sources: every sep_set_kernel statement of the six files, a statement inside a launch macro counted once per use
     of the macro, contributes the string literals it chooses between"""
     def names(fname, macros):
         src = open(os.path.join(CSRC, fname)).read()
@@ -84,11 +85,14 @@ def test_the_ledger_lists_every_launch_line_of_the_dispatchers():
         assert len(in_macros) == len(macros), (fname, in_macros)
         uses = sum(per_use * (len(re.findall(r"\b" + m + r"\(", src)) - 1) for m, per_use in macros.items())      # (- 1: the #define itself)
         return plain, uses
-    assert names("stream.hip", {"SEP_DWF": 2, "SEP_DWB2": 2, "SEP_DEB": 2}) == (23, 3 * 2 + 8 * 2 + 3 * 2)
+    stream = {"filterbank.hip": names("filterbank.hip", {"SEP_DEB": 2}), "tcn.hip": names("tcn.hip", {"SEP_DWF": 2, "SEP_DWB2": 2}),
+              "gln.hip": names("gln.hip", {}), "depthwise.hip": names("depthwise.hip", {})}
+    assert stream == {"filterbank.hip": (7, 3 * 2), "tcn.hip": (4, 3 * 2 + 8 * 2), "gln.hip": (4, 0), "depthwise.hip": (8, 0)}
+    assert tuple(sum(v[i] for v in stream.values()) for i in (0, 1)) == (23, 3 * 2 + 8 * 2 + 3 * 2)      # the four together: as many as the one file they were cut from
     assert names("cln.hip", {"SEP_CLF": 1, "SEP_CLS": 1, "SEP_CLB": 1}) == (3, 12)
     assert names("causal.hip", {"SEP_CDF": 1, "SEP_CDW": 1}) == (0, 8)
     assert len(SM.INSTANCES) == len(set(SM.INSTANCES)) == 23 + 28 + 3 + 12 + 8
-    for f in ("stream.hip", "cln.hip", "causal.hip"):                  # and every literal name in the sources is one of the ledger's
+    for f in tuple(stream) + ("cln.hip", "causal.hip"):                # and every literal name in the sources is one of the ledger's
         for lit in re.findall(r'"([^"]*)"', " ".join(s for s in re.findall(r"sep_set_kernel\(([^;]*)\);", open(os.path.join(CSRC, f)).read()) if "#" not in s and "NAME" not in s)):
             assert lit in SM.INSTANCES, lit
 

@@ -1,5 +1,5 @@
-"""GPU: every kernel instance behind the streaming entry points of csrc/stream.hip, csrc/cln.hip and csrc/causal.hip, reached BY NAME on the
-MI355X and compared with a float64 restatement of the call's contract, row by row and sum by sum (tests/stream_matrix.py: the ledger, the
+"""GPU: every kernel instance behind the streaming entry points of csrc/filterbank.hip, csrc/tcn.hip, csrc/gln.hip, csrc/depthwise.hip,
+csrc/cln.hip and csrc/causal.hip, reached BY NAME on the MI355X and compared with a float64 restatement of the call's contract, row by row and sum by sum (tests/stream_matrix.py: the ledger, the
 case matrix -- the same cases tests/test_stream_instances_cpu.py runs on the host simulation --, the reference, the metric and the measured
 bounds).  The default environment runs in this process, one pytest case per family; each of the four A/B switches, read once per process, gets
 one child process that runs the affected families' cases under it: one after another, each under its own time limit; the first child that

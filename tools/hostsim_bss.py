@@ -6,7 +6,7 @@ length or the buffers' ends, writes beyond the scratch, undefined arithmetic.
 
     python tools/hostsim_bss.py [--asan]
 
-build_library(workdir) gives tests/test_bss_eval_cpu.py a host-simulation library of csrc/loss.hip alone (a few seconds instead of the
+build_library(workdir) gives tests/test_bss_eval_cpu.py a host-simulation library of csrc/loss.hip and csrc/runtime.hip alone (a few seconds instead of the
 minute the whole of csrc/ takes)."""
 import os
 import subprocess
@@ -19,10 +19,12 @@ HOSTSIM_DIR = os.path.join(hostsim.ROOT, "tools", "hostsim")
 
 
 def _sources(d):
-    """the host copy of loss.hip (the kernels and the library's error slot) in `d`, plus the simulation's runtime"""
-    cpp = os.path.join(d, "loss.cpp")
-    open(cpp, "w").write(hostsim.host_copy("loss.hip"))
-    return [cpp, os.path.join(HOSTSIM_DIR, "sim_main.cpp")]
+    """the host copies of loss.hip (the kernels) and runtime.hip (the library's error slot) in `d`, plus the simulation's runtime"""
+    out = []
+    for f in ("loss", "runtime"):
+        out.append(os.path.join(d, f + ".cpp"))
+        open(out[-1], "w").write(hostsim.host_copy(f + ".hip"))
+    return out + [os.path.join(HOSTSIM_DIR, "sim_main.cpp")]
 
 
 def _includes(d):
@@ -30,7 +32,7 @@ def _includes(d):
 
 
 def build_library(workdir):
-    """-> path of a shared library with the entry points of csrc/loss.hip, for hostsim.HostSimBackend"""
+    """-> path of a shared library with the entry points of csrc/loss.hip and csrc/runtime.hip, for hostsim.HostSimBackend"""
     cxx = hostsim.compiler()
     if cxx is None:
         raise RuntimeError("hostsim needs clang++")

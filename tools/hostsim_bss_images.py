@@ -6,7 +6,7 @@ length, a frame's end or the buffers' ends, writes beyond the scratch, undefined
 
     python tools/hostsim_bss_images.py [--asan]
 
-The host-simulation library for tests/test_bss_images_cpu.py is tools/hostsim_bss.py::build_library (csrc/loss.hip alone)."""
+The host-simulation library for tests/test_bss_images_cpu.py is tools/hostsim_bss.py::build_library (csrc/loss.hip and csrc/runtime.hip alone)."""
 import os
 import subprocess
 import sys

@@ -13,7 +13,7 @@ import tempfile
 
 import hostsim
 
-FILES = ("causal", "online", "loss")        # loss.hip holds the library's error slot (sep_set_error / sep_last_error)
+FILES = ("causal", "online", "runtime")     # runtime.hip holds the library's error slot (sep_set_error / sep_last_error)
 
 
 def main():

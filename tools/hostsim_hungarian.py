@@ -7,14 +7,14 @@ an index from a poisoned comparison, undefined arithmetic.
 
     python tools/hostsim_hungarian.py [--asan]
 
-build_library(workdir) gives tests/test_hungarian_cpu.py a host-simulation library of csrc/loss.hip alone."""
+build_library(workdir) gives tests/test_hungarian_cpu.py a host-simulation library of csrc/loss.hip and csrc/runtime.hip alone."""
 import os
 import subprocess
 import sys
 import tempfile
 
 import hostsim
-from hostsim_bss import HOSTSIM_DIR, _includes, _sources, build_library      # noqa: F401  (the same translation unit: csrc/loss.hip)
+from hostsim_bss import HOSTSIM_DIR, _includes, _sources, build_library      # noqa: F401  (the same translation units: csrc/loss.hip, csrc/runtime.hip)
 
 
 def main():

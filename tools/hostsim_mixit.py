@@ -6,14 +6,14 @@ row's end, writes beyond the scratch or the outputs, undefined arithmetic.
 
     python tools/hostsim_mixit.py [--asan]
 
-build_library(workdir) gives tests/test_mixit_cpu.py a host-simulation library of csrc/loss.hip alone."""
+build_library(workdir) gives tests/test_mixit_cpu.py a host-simulation library of csrc/loss.hip and csrc/runtime.hip alone."""
 import os
 import subprocess
 import sys
 import tempfile
 
 import hostsim
-from hostsim_bss import HOSTSIM_DIR, _includes, _sources, build_library      # noqa: F401  (the same translation unit: csrc/loss.hip)
+from hostsim_bss import HOSTSIM_DIR, _includes, _sources, build_library      # noqa: F401  (the same translation units: csrc/loss.hip, csrc/runtime.hip)
 
 
 def main():

@@ -1,4 +1,4 @@
-"""Development tool: the resampling kernels (csrc/resample.hip: sep_resample_fwd, sep_resample_stream_fwd; csrc/loss.hip beside them holds the
+"""Development tool: the resampling kernels (csrc/resample.hip: sep_resample_fwd, sep_resample_stream_fwd; csrc/runtime.hip beside them holds the
 library's error slot and the kernel-name observable) compiled for the host (tools/hostsim.py::host_copy, the stand-in HIP header of
 tools/hostsim/include) and linked with tools/hostsim/resample_main.cpp into ONE PROGRAM that runs both kernels over the rate pairs and lengths of
 tests/test_resample_gpu.py on exactly-sized buffers against plain double loops over the full table, and every stream against the offline call
@@ -7,7 +7,7 @@ is involved in the run): reads outside [0, T) of a row or beyond the table, firs
 
     python tools/hostsim_resample.py [--asan]
 
-build_library(workdir) gives tests/test_resample_cpu.py a host-simulation library of csrc/resample.hip and csrc/loss.hip alone."""
+build_library(workdir) gives tests/test_resample_cpu.py a host-simulation library of csrc/resample.hip and csrc/runtime.hip alone."""
 import os
 import subprocess
 import sys
@@ -16,11 +16,11 @@ import tempfile
 import hostsim
 from hostsim_bss import HOSTSIM_DIR, _includes
 
-FILES = ("resample", "loss")
+FILES = ("resample", "runtime")
 
 
 def _sources(d):
-    """the host copies of resample.hip and loss.hip in `d`, plus the simulation's runtime"""
+    """the host copies of resample.hip and runtime.hip in `d`, plus the simulation's runtime"""
     out = []
     for f in FILES:
         out.append(os.path.join(d, f + ".cpp"))
@@ -29,7 +29,7 @@ def _sources(d):
 
 
 def build_library(workdir):
-    """-> path of a shared library with the entry points of csrc/resample.hip and csrc/loss.hip, for hostsim.HostSimBackend"""
+    """-> path of a shared library with the entry points of csrc/resample.hip and csrc/runtime.hip, for hostsim.HostSimBackend"""
     cxx = hostsim.compiler()
     if cxx is None:
         raise RuntimeError("hostsim needs clang++")

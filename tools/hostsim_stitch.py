@@ -1,5 +1,5 @@
 """Development tool: the stitching kernels (csrc/stitch.hip: sep_stitch_cost, sep_stitch_chain, sep_stitch_ola) and sep_assign beside them
-(csrc/loss.hip, which also holds the library's error slot) compiled for the host (tools/hostsim.py::host_copy, the stand-in HIP header of
+(csrc/loss.hip; csrc/runtime.hip holds the library's error slot) compiled for the host (tools/hostsim.py::host_copy, the stand-in HIP header of
 tools/hostsim/include) and linked with tools/hostsim/stitch_main.cpp into ONE PROGRAM that runs the three kernels over the window geometries of
 tests/test_longform_gpu.py at n in {1, 3, 9, 20, 64} on exactly-sized buffers against plain double loops, and the four launches in a row on
 scrambled windows.  With --asan the program is built with -fsanitize=address,undefined (the runtime is linked in; nothing is preloaded and no
@@ -8,7 +8,7 @@ permutation entry, undefined arithmetic.
 
     python tools/hostsim_stitch.py [--asan]
 
-build_library(workdir) gives tests/test_longform_cpu.py a host-simulation library of csrc/stitch.hip and csrc/loss.hip alone."""
+build_library(workdir) gives tests/test_longform_cpu.py a host-simulation library of csrc/stitch.hip, csrc/loss.hip and csrc/runtime.hip alone."""
 import os
 import subprocess
 import sys
@@ -17,11 +17,11 @@ import tempfile
 import hostsim
 from hostsim_bss import HOSTSIM_DIR, _includes
 
-FILES = ("stitch", "loss")
+FILES = ("stitch", "loss", "runtime")
 
 
 def _sources(d):
-    """the host copies of stitch.hip and loss.hip in `d`, plus the simulation's runtime"""
+    """the host copies of stitch.hip, loss.hip and runtime.hip in `d`, plus the simulation's runtime"""
     out = []
     for f in FILES:
         out.append(os.path.join(d, f + ".cpp"))
@@ -30,7 +30,7 @@ def _sources(d):
 
 
 def build_library(workdir):
-    """-> path of a shared library with the entry points of csrc/stitch.hip and csrc/loss.hip, for hostsim.HostSimBackend"""
+    """-> path of a shared library with the entry points of csrc/stitch.hip, csrc/loss.hip and csrc/runtime.hip, for hostsim.HostSimBackend"""
     cxx = hostsim.compiler()
     if cxx is None:
         raise RuntimeError("hostsim needs clang++")
