@@ -15,6 +15,11 @@ sisdr: negative SI-SDR).  Validation scores mixtures of mixtures of the validati
 `--criterion hungarian` trains on isolated sources like `sisdr`, with the best permutation found as an O(n^3) assignment problem
 (criterion/hungarian.py) instead of PIT's table of n! permutations: any `--n_sources`.  `--hungarian_measure` picks what scores a pair
 (sisdr: negative SI-SDR; snr: the thresholded SNR, 30 dB).  Validation uses the same criterion.
+
+`--dynamic_mixing 1` trains on fresh mixtures every step (sepkernels.mixing.DynamicMixer): the utterances behind `--train_list_path` (its s1 .. sn
+files, each kept once; recipes.dynamic_mixing.corpus_from_mix_list) are decoded once and kept on the device, and every step draws new speakers,
+crops and gains there -- `--dm_gain_db G` (default 2.5: gains uniform in [-G, G] dB around the common level), `--dm_steps_per_epoch N` (default:
+the length of the fixed loader it replaces), `--dm_seed S` (default: --seed).  Validation stays on the fixed list.  Not with --criterion mixit.
 """
 import argparse
 import os
@@ -79,6 +84,11 @@ def build_parser():
     ap.add_argument("--overwrite", type=_flag, default=False)
     ap.add_argument("--num_workers", type=int, default=2)
     ap.add_argument("--seed", type=int, default=111)
+    ap.add_argument("--use_cuda", type=_flag, default=True, help="0: model, corpus and batches stay on the CPU, for a backend that takes CPU tensors (the test suite's emulator); the HIP library refuses them")
+    ap.add_argument("--dynamic_mixing", type=_flag, default=False, help="train on fresh mixtures drawn on the device every step")
+    ap.add_argument("--dm_gain_db", type=float, default=2.5, help="with --dynamic_mixing: gains are drawn from [-G, G] dB")
+    ap.add_argument("--dm_steps_per_epoch", type=int, default=None, help="with --dynamic_mixing: steps per epoch (default: the length of the fixed loader)")
+    ap.add_argument("--dm_seed", type=int, default=None, help="with --dynamic_mixing: the seed of the draw (default: --seed)")
     return ap
 
 
@@ -106,10 +116,13 @@ def main(argv=None):
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         dist.init_process_group("nccl" if torch.cuda.is_available() else "gloo", rank=rank, world_size=world)
     torch.manual_seed(args.seed)
-    if not torch.cuda.is_available():
-        raise RuntimeError("the fused Conv-TasNet path needs an MI355X (no CPU fallback)")
-    torch.cuda.set_device(local_rank)
-    dev = torch.device("cuda", local_rank)
+    if not args.use_cuda:
+        dev = torch.device("cpu")
+    else:
+        if not torch.cuda.is_available():
+            raise RuntimeError("the fused Conv-TasNet path needs an MI355X (no CPU fallback)")
+        torch.cuda.set_device(local_rank)
+        dev = torch.device("cuda", local_rank)
 
     samples = int(args.sample_rate * args.duration)
     train_set = WaveTrainDataset(args.train_wav_root, args.train_list_path, samples=samples, overlap=samples // 2, n_sources=args.n_sources)
@@ -129,6 +142,19 @@ def main(argv=None):
 
     loader = {"train": train_loader(0), "valid": EvalDataLoader(valid_set, batch_size=1, shuffle=False)}
     args.reshard = train_loader if world > 1 or mixit else None      # every rank trains on a different subset each epoch; MixIT re-pairs
+    if args.dynamic_mixing:
+        if mixit:
+            raise ValueError("--dynamic_mixing draws isolated sources; --criterion mixit trains on mixtures of the list's mixtures")
+        from sepkernels.mixing import DynamicMixer
+        from .dynamic_mixing import corpus_from_mix_list
+        corpus = corpus_from_mix_list(args.train_wav_root, args.train_list_path, args.n_sources, device=dev)
+        if rank == 0:
+            print("Dynamic mixing: {} utterances of {} speakers, {:.1f} MB on {}.".format(corpus.num_utterances, corpus.num_speakers,
+                                                                                       corpus.samples.numel() * corpus.samples.element_size() / 1e6, dev))
+        args.dynamic_mixer = DynamicMixer(corpus, n_sources=args.n_sources, samples=samples, batch_size=args.batch_size,
+                                          seed=args.seed if args.dm_seed is None else args.dm_seed, gain_db=(-abs(args.dm_gain_db), abs(args.dm_gain_db)),
+                                          gain_steps=256 if args.dm_gain_db else 1, rank=rank, world=world)
+        args.dynamic_steps_per_epoch = args.dm_steps_per_epoch
 
     stride = args.kernel_size // 2 if args.stride is None else args.stride
     model = ConvTasNet(args.n_basis, args.kernel_size, stride=stride, enc_basis=args.enc_basis, dec_basis=args.dec_basis,

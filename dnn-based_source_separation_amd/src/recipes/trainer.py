@@ -8,7 +8,9 @@ after 10 the run stops; `--continue_from` resumes, an existing `best.pth` is ref
 
 What is different: one process per GPU (torchrun) instead of nn.DataParallel, the step is
 `sepkernels.train.FusedTrainStep` (forward + PIT + backward + one RCCL all-reduce + fused clip/Adam on flat buffers),
-batches arrive through a pinned, asynchronous prefetcher, and only rank 0 validates / writes files.
+batches arrive through a pinned, asynchronous prefetcher, and only rank 0 validates / writes files.  With `args.dynamic_mixer` (a
+sepkernels.mixing.DynamicMixer) the training pass takes `args.dynamic_steps_per_epoch` fresh batches from the mixer in place of the loader
+(validation stays on the fixed list); the checkpoint then carries `mixer` = {seed, step} and a resumed run continues the stream.
 
 Checkpoint format = the reference's (driver.py:208-226): `model.get_config()` keys + `state_dict`, `optim_dict`
 (torch.optim.Adam layout, so either side can resume the other's file), `best_loss`, `no_improvement`, `train_loss`,
@@ -42,7 +44,7 @@ def _rank():
 class Trainer:
     def __init__(self, model, loader, pit_criterion, args):
         """loader = {'train': ..., 'valid': ...}; args: namespace with model_dir, loss_dir, sample_dir, epochs, lr,
-        max_norm, continue_from, overwrite, sample_rate (and optionally weight_decay, use_cuda)."""
+        max_norm, continue_from, overwrite, sample_rate (and optionally weight_decay, use_cuda, dynamic_mixer, dynamic_steps_per_epoch)."""
         self.model, self.pit_criterion = model, pit_criterion
         self.train_loader, self.valid_loader = loader["train"], loader["valid"]
         self.device = next(model.parameters()).device
@@ -70,6 +72,10 @@ class Trainer:
         self.step = FusedTrainStep(model, pit_criterion, lr=args.lr, weight_decay=getattr(args, "weight_decay", 0.0),
                                    max_norm=args.max_norm or 0.0, auto_record=os.environ.get("SEPK_SEQUENCE", "1") != "0")
         self.reshard = getattr(args, "reshard", None)       # callable(epoch) -> this rank's train loader for that epoch, or None
+        self.mixer = getattr(args, "dynamic_mixer", None)   # fresh mixtures every step in place of the train loader, or None
+        if self.mixer is not None:
+            steps = getattr(args, "dynamic_steps_per_epoch", None)
+            self.dynamic_steps = int(steps) if steps else len(self.train_loader)      # default: the length of the fixed loader it replaces
         self.train_loss = torch.empty(self.epochs)
         self.valid_loss = torch.empty(self.epochs)
         if getattr(args, "continue_from", None):
@@ -82,6 +88,8 @@ class Trainer:
             self.no_improvement = ck["no_improvement"]
             model.load_state_dict(ck["state_dict"])
             self.step.load_optim_state_dict(ck["optim_dict"])
+            if self.mixer is not None and "mixer" in ck:
+                self.mixer.load_state_dict(ck["mixer"])
         else:
             self.start_epoch = 0
             self.best_loss = float("infinity")
@@ -126,6 +134,8 @@ class Trainer:
 
     def run_one_epoch_train(self, epoch):
         self.model.train()
+        if self.mixer is not None:
+            return self._run_one_epoch_dynamic(epoch)
         if self.reshard is not None:                        # a fresh shard of the training set per epoch (same permutation on every rank)
             self.train_loader = self.reshard(epoch)
         total = torch.zeros((), device=self.device, dtype=torch.float64)   # no .item() per step: the step stays asynchronous
@@ -140,6 +150,20 @@ class Trainer:
             dist.all_reduce(total)
             total /= dist.get_world_size()
         return total.item() / max(n, 1)
+
+    def _run_one_epoch_dynamic(self, epoch):
+        """the training pass fed by the mixer: the mixer, then the step (the host does no per-step data work)"""
+        total = torch.zeros((), device=self.device, dtype=torch.float64)
+        for idx in range(self.dynamic_steps):
+            mixture, sources = self.mixer()[:2]
+            loss = self.step(mixture.to(self.device), sources.to(self.device))
+            total += loss.double()
+            if (idx + 1) % 100 == 0 and self.is_main:
+                print("[Epoch {}/{}] iter {}/{} loss: {:.5f}".format(epoch + 1, self.epochs, idx + 1, self.dynamic_steps, loss.item()), flush=True)
+        if _is_dist():
+            dist.all_reduce(total)
+            total /= dist.get_world_size()
+        return total.item() / max(self.dynamic_steps, 1)
 
     def run_one_epoch_eval(self, epoch):
         """Rank 0 validates every utterance (B = 1, variable length); the scalar is broadcast so all ranks take the same
@@ -182,6 +206,8 @@ class Trainer:
         ck["train_loss"] = self.train_loss
         ck["valid_loss"] = self.valid_loss
         ck["epoch"] = epoch + 1
+        if self.mixer is not None:
+            ck["mixer"] = self.mixer.state_dict()
         torch.save(ck, model_path)
 
 

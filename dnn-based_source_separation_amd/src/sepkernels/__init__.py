@@ -22,6 +22,7 @@ LSTM_INTERLEAVED = 0x400       # sep_lstm_fwd / sep_lstm_bwd with reverse = 2: h
 STATS_SLOTS = 16   # SEP_STATS_SLOTS: gLN statistics are double[B][STATS_SLOTS][2]
 ARRIVE_INTS = 17   # SEP_ARRIVE_INTS: arrival counters of the gLN-backward publishers, int[B][ARRIVE_INTS]
 ARITH_F32, ARITH_BF16X6, ARITH_F16X3 = 0, 1, 2     # SEP_ARITH_*: how sep_pw_gemm forms its fp32 products (include/sepkernels.h)
+MIX_MAX_SOURCES, MIX_GUARD, MIX_INT16, MIX_F32 = 8, 16, 0, 1      # SEP_MIX_*: what sep_mix_draw / sep_mix_render take, the corpus's guard zeros, its sample kinds
 MIXIT_SLAB = 2048  # SEP_MIXIT_SLAB: samples behind one partial sum of sep_mixit_gram
 MIXIT_MAX_EST, MIXIT_MAX_MIX, MIXIT_MAX_CODES = 16, 8, 65536       # SEP_MIXIT_MAX_*: what sep_mixit_search takes
 PAIR_SLAB = 2048   # SEP_PAIR_SLAB: samples behind one partial sum of sep_pair_gram
@@ -261,6 +262,9 @@ SIGNATURES = {
     # sample-rate conversion (ABI 23, additive): rows of whole signals, rows of an online call with a history per stream
     "sep_resample_fwd": [_vp, _L, _vp, _vp, _vp, _L, _I, _L, _L] + [_I] * 4 + [_vp],
     "sep_resample_stream_fwd": [_vp] * 6 + [_I] * 7 + [_vp],
+    # dynamic mixing from a device-resident corpus (ABI 23, additive): the plan of a batch from a step count in device memory, the gather-scale-sum pass
+    "sep_mix_draw": [_vp, _vp, _I, _I, _vp, _I, _vp, _vp, _I, _vp, _vp, _I, _vp, _L, _L, _L, _I, _I, _I, _vp, _vp, _vp],
+    "sep_mix_render": [_vp, _I, _vp, _I, _vp, _vp, _I, _vp, _vp, _I, _I, _I, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_last_kernel": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
              "sep_gln_tokens_ws_bytes": ctypes.c_size_t, "sep_online_state_row_bytes": ctypes.c_size_t, "sep_bss_scratch_bytes": ctypes.c_size_t, "sep_bss_image_scratch_bytes": ctypes.c_size_t,
@@ -439,7 +443,7 @@ def _check(rc, name):
 
 def last_kernel():
     """Name of the kernel instance this thread's last pw_gemm / pw_wgrad / pw_wgrad_batch launch, or its last call of a streaming dispatcher
-    (encoder_fwd, dwconv_fwd / _bwd, decoder_fwd / _bwd, depthwise_*, split_rows, gln_tokens_*, cln_*, depthwise_cln_*, resample_*), went to
+    (encoder_fwd, dwconv_fwd / _bwd, decoder_fwd / _bwd, depthwise_*, split_rows, gln_tokens_*, cln_*, depthwise_cln_*, resample_*, mix_render), went to
     (sep_last_kernel: family and template arguments, e.g. 'pc<4,1,SEP_PRO_GLN_PRELU,false,SEP_EPI_RESIDUAL>', 'dwconv_bwd_row<3,8,true>',
     'decoder_bwd<16,2>/nz1'), '' before the first one.  Not a launch: never recorded."""
     return load().sep_last_kernel().decode()
@@ -999,6 +1003,24 @@ class HipBackend:
     def resample_stream_fwd(self, chunk, table, first, history, y, slots, A, num_streams, m, o, u, width, Kc):
         _check(load().sep_resample_stream_fwd(_ptr(chunk, _f32), _ptr(table, _f32), _ptr(first, torch.int32), _ptr(history, _f32), _ptr(y, _f32),
                                               _ptr(slots, torch.int32), A, num_streams, m, o, u, width, Kc, _stream()), "sep_resample_stream_fwd")
+
+    # ... dynamic mixing (sepkernels/mixing.py): samples int16 or fp32 (flat, guard zeros at both ends), offsets (U + 1,) int64, spk_first (S + 1,) int32,
+    # level (U,) fp32, gain_table (G,) fp32, counter (1,) int64; the noise twins or None; plan (B, R, 4) int64, gain (B, R) fp32, R = n or n + 1
+    def mix_draw(self, offsets, spk_first, U, S, noise_offsets, U_noise, level, gain_table, G, noise_level, noise_gain_table, G_noise, counter, seed,
+                 item_stride, item_first, B, n, T, plan, gain):
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF                  # read as unsigned by the library: handed over as the int64 of the same bits
+        _check(load().sep_mix_draw(_ptr(offsets, torch.int64), _ptr(spk_first, torch.int32), U, S, _ptr(noise_offsets, torch.int64), U_noise, _ptr(level, _f32),
+                                   _ptr(gain_table, _f32), G, _ptr(noise_level, _f32), _ptr(noise_gain_table, _f32), G_noise, _ptr(counter, torch.int64),
+                                   seed - (1 << 64) if seed >> 63 else seed, item_stride, item_first, B, n, T, _ptr(plan, torch.int64), _ptr(gain, _f32), _stream()),
+               "sep_mix_draw")
+
+    def mix_render(self, samples, offsets, U, noise_samples, noise_offsets, U_noise, plan, gain, B, n, T, sources, mixture, noise):
+        kind = {torch.int16: MIX_INT16, torch.float32: MIX_F32}.get(samples.dtype)
+        if kind is None or (noise_samples is not None and noise_samples.dtype != samples.dtype):
+            raise SepKernelsError("mix_render takes int16 or float32 samples, the noise corpus of the same kind")
+        _check(load().sep_mix_render(_ptr(samples), kind, _ptr(offsets, torch.int64), U, _ptr(noise_samples), _ptr(noise_offsets, torch.int64), U_noise,
+                                     _ptr(plan, torch.int64), _ptr(gain, _f32), B, n, T, _ptr(sources, _f32), _ptr(mixture, _f32), _ptr(noise, _f32), _stream()),
+               "sep_mix_render")
 
 
 _backend = HipBackend()

@@ -971,6 +971,64 @@ int sep_resample_fwd(const float* x, int64_t x_pitch, const float* table, const 
 int sep_resample_stream_fwd(const float* chunk, const float* table, const int32_t* first, float* history, float* y, const int32_t* slots, int A,
                             int num_streams, int m, int o, int u, int width, int Kc, sep_stream_t stream);
 
+/* ---- Dynamic mixing from a device-resident corpus (ABI 23, additive; csrc/mixing.hip, sepkernels/mixing.py) --------------------------------------
+ * A training batch of fresh mixtures per step -- new speakers, utterances, crops and gains every time -- drawn and rendered on the device from a
+ * corpus that lives there (the whole wsj0 si_tr_s set is about 1.7 GB as int16).  The reference mixes on the fly only for music
+ * (egs/musdb18/<model>/local/train.py with src/utils/augmentation.py) and in its tutorials (egs/tutorials/common/src/dataset.py:44).
+ * The corpus (the CALLER's; sepkernels/mixing.py::DeviceCorpus builds it):
+ *     samples    ONE flat tensor of all utterances, int16 (SEP_MIX_INT16, a sample is pcm 2^-15) or fp32 (SEP_MIX_F32); at least SEP_MIX_GUARD zero
+ *                elements in front of the first utterance and behind the last, so that whole aligned 16-byte words may be loaded
+ *     offsets    int64, U + 1 entries: utterance u is samples[offsets[u] : offsets[u + 1]], 1 <= its length < 2^31; offsets[0] is the guard length
+ *     spk_first  int32, S + 1 entries: utterances are sorted by speaker, speaker s owns utterances [spk_first[s], spk_first[s + 1]), at least one
+ *     level      fp32, U entries: ref_rms / rms_u (plain RMS over the whole utterance in fp64 on the host, NOT the ITU active level of wsj0-mix's Matlab
+ *                scripts; 0 for a silent utterance, 1 everywhere without normalisation)
+ * THE DRAW.  Counter-based, no generator state, all in wrapping uint64:
+ *     mix64(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *     word(seed, item, k) = mix64(mix64(seed + 0x9E3779B97F4A7C15 * (item + 1)) + k)
+ *     below(w, m) = ((w >> 32) * m) >> 32                                   1 <= m < 2^31
+ *     item = step * item_stride + item_first + b                            (item_stride = the global batch, item_first = rank * B)
+ * For item b and source i < n, with `chosen` the ascending list of the speakers already taken:
+ *     speaker     r = below(word(.., i), S - i); for c in chosen, ascending: if r >= c then r += 1; s_i = r, and r is inserted into chosen -- the sources
+ *                 of a mixture have distinct speakers, drawn uniformly without replacement; every loop is bounded by n
+ *     utterance   u = spk_first[s] + below(word(.., n + i), spk_first[s + 1] - spk_first[s])
+ *     position    len = offsets[u + 1] - offsets[u], w = word(.., 2 n + i): if len >= T then start = below(w, len - T + 1), lead = 0; else start = 0,
+ *                 lead = below(w, T - len + 1) -- a short utterance is placed at a random offset inside the segment, zeros around it
+ *     gain index  g = below(word(.., 3 n + i), G);   gain[b][i] = level[u] * gain_table[g], ONE fp32 multiply
+ *     noise row   (with a noise index, the WHAM recipes' third signal; no speaker structure) u = below(word(.., 4 n), U_noise), the position from draw
+ *                 4 n + 1, the gain index from draw 4 n + 2 into noise_gain_table of G_noise entries, gain = noise_level[u] * noise_gain_table[g]
+ * gain_table[j] = (float)10^((lo + (hi - lo) j / (G - 1)) / 20) is built by the host in fp64: nothing transcendental is evaluated on the device, so the
+ * draw is bit-exact against a restatement in Python integers.  Known answers:
+ *     word(1234, 0, 0) = 0x2851ddd6c202938b   word(1234, 0, 1) = 0xf344a9a461c929aa   word(1234, 1, 0) = 0xc4c7e6b923620b24
+ *     word(1234, 1, 1) = 0x22531db8ef59e66f   word(0, 0, 0) = 0x48218226ff3cd4bf      word(2^63, 2^40 + 3, 31) = 0x568966ec49cd65d1
+ *   sep_mix_draw    writes plan int64 (B, R, 4) = {utterance, start, lead, gain index} and gain fp32 (B, R); R = n without a noise index (noise_offsets
+ *                   NULL, U_noise 0), n + 1 with one.  `seed` is read as unsigned.  The step lives in device memory: counter[0] is the step of this call
+ *                   and the kernel leaves counter[0] + 1, so a recorded call replays into the NEXT batch (as sep_adam_step_dev does with its step
+ *                   count).  One workgroup whose threads loop over the items; every thread reads the counter, then a barrier, then one thread stores
+ *                   the increment: no atomics.  The index is device memory the library cannot look at: a speaker's count below 1 is read as 1, an
+ *                   utterance outside [0, U) as the nearest end, a length outside [1, 2^31) likewise.
+ *   sep_mix_render  writes sources (B, n, T), mixture (B, 1, T) and, if `noise` is not NULL (then the plan has n + 1 rows and noise_samples,
+ *                   noise_offsets come with it), the noise row (B, 1, T) from a plan:
+ *                       src[b][i][t] = gain[b][i] * ((float)pcm[offsets[u] + start + t - lead] * scale)   where lead <= t and t - lead < len - start,
+ *                                      +0.0f elsewhere;   scale = 2^-15 for int16 (that product is exact), 1 for fp32: one rounding per sample
+ *                       mixture[b][0][t] = ((src_0 + src_1) + src_2) + ... in ascending i in fp32, the noise row added last
+ *                   Every element is written once by the thread that owns it: no atomics, two runs give the same bits.  The plan is device memory the
+ *                   library cannot look at: u is clamped into [0, U), start into [0, len - 1], and the predicate keeps every read inside the utterance
+ *                   whatever lead holds, so no plan can index outside the storage.  Instances (sep_last_kernel): "mix_render_vec<int16,8>" and
+ *                   "mix_render_vec<float,4>" when T % 4 == 0 and the outputs are 16-byte aligned (a thread owns 8 or 4 consecutive samples of every
+ *                   row, 16-byte stores; for int16 aligned 16-byte loads selected by the row's misalignment, which is uniform per (item, source) -- the
+ *                   guard zeros are there for this), "mix_render_scalar<int16>" and "mix_render_scalar<float>" for everything else.  All offsets are 64-bit.
+ * Refused with a message before any launch: a null pointer, n outside [1, SEP_MIX_MAX_SOURCES], n > S, S > U, B outside [1, 65535], T < 1, G < 1, an
+ * unknown sample kind, a noise index without its levels and table (draw), a noise row without its samples and index or the other way round (render). */
+#define SEP_MIX_MAX_SOURCES 8
+#define SEP_MIX_GUARD 16
+#define SEP_MIX_INT16 0
+#define SEP_MIX_F32 1
+int sep_mix_draw(const int64_t* offsets, const int32_t* spk_first, int U, int S, const int64_t* noise_offsets, int U_noise, const float* level,
+                 const float* gain_table, int G, const float* noise_level, const float* noise_gain_table, int G_noise, int64_t* counter, int64_t seed,
+                 int64_t item_stride, int64_t item_first, int B, int n, int T, int64_t* plan, float* gain, sep_stream_t stream);
+int sep_mix_render(const void* samples, int kind, const int64_t* offsets, int U, const void* noise_samples, const int64_t* noise_offsets, int U_noise,
+                   const int64_t* plan, const float* gain, int B, int n, int T, float* sources, float* mixture, float* noise, sep_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
