@@ -206,3 +206,5 @@ int sep_pw_wgrad_pc(const sep_wgrad_desc* d, hipStream_t stream);
 // wgrad_pc16.hip: the same in the scaled two-part fp16 arithmetic (SEP_ARITH_F16X3; same contract)
 int sep_pw_wgrad_pc16(const sep_wgrad_desc* d, hipStream_t stream);
 int sep_pw_wgrad_pc16_batch(const sep_wgrad_desc* ds, int n, hipStream_t stream);
+// gemm.hip: the launch of sep_pw_wgrad's register-staged fallback, whose kernel sits beside pw_gemm_kernel (checks, grid and name: the caller's)
+void sep_pw_wgrad_staged(const sep_wgrad_desc* d, int grid, hipStream_t stream);

@@ -1,9 +1,10 @@
-// What the five 1x1-contraction translation units of libsepkernels (gemm.hip, gemm_coop.hip, gemm_pc.hip, wgrad_pc.hip, wgrad_pc16.hip)
+// What the six 1x1-contraction translation units of libsepkernels (gemm.hip, wgrad.hip, gemm_coop.hip, gemm_pc.hip, wgrad_pc.hip, wgrad_pc16.hip)
 // share, each piece written once.  Device side: DPP row sums, the LDS-transposed float4 epilogue, LDS-DMA issue / wait / barrier helpers,
 // the two partition rules of the grids (XCD-aware block decode, slabs of the weight gradients) and the arithmetic contract of
 // SEP_ARITH_F16X3 / SEP_ARITH_BF16X6: the MFMA wrappers, the two-part fp16 and three-part bf16 splits, the running scale exponent and the
-// single-instruction wave primitives that go with them.  Host side: the dispatchers' tables (which fused instances exist, which
-// prologues, what the producer / consumer weight-gradient kernels take) and the grid sizes that match the decode.  gfx950 only.
+// single-instruction wave primitives that go with them; the output tile and the fp32 chunk product of the register-staged kernels.
+// Host side: the dispatchers' tables (which fused instances exist, which prologues, what the producer / consumer weight-gradient
+// kernels take) and the grid sizes that match the decode.  gfx950 only.
 #pragma once
 #include "common.hpp"
 #include <type_traits>
@@ -542,7 +543,7 @@ __device__ __forceinline__ float max_lane_xor1(const float m) {      // max(m, m
 }
 
 // SEP_ARITH_BF16X6: fp32 products from the EXACT three-way bf16 split of both operands, x = hi + mid + lo with each part a truncated
-// bf16 (8 + 8 + 8 significand bits), six of the nine part products on v_mfma_f32_32x32x16_bf16 (gemm.hip, wgrad_pc.hip).
+// bf16 (8 + 8 + 8 significand bits), six of the nine part products on v_mfma_f32_32x32x16_bf16 (gemm.hip, wgrad.hip, wgrad_pc.hip).
 // two fp32 values -> their (hi, mid, lo) parts packed {x0 low half, x1 high half}; hi + mid + lo == x exactly: 11 VALU instructions
 __device__ __forceinline__ void split3_pair(const float x0, const float x1, unsigned& hi, unsigned& mid, unsigned& lo) {
     const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
@@ -552,6 +553,67 @@ __device__ __forceinline__ void split3_pair(const float x0, const float x1, unsi
     mid = __builtin_amdgcn_perm(v1, v0, 0x07060302u);
     const float q0 = r0 - __uint_as_float(v0 & 0xffff0000u), q1 = r1 - __uint_as_float(v1 & 0xffff0000u);
     lo = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
+}
+
+// Common to all kernels of gemm.hip and wgrad.hip: 128x128 output tile, each wave a 64x64 sub-tile = 2x2 32x32 MFMA accumulators (64 VGPRs);
+// the normalised tensors v1, v2 of the reference never exist in HBM; workgroups that share an X column tile are placed
+// on the same XCD (blockIdx % 8) so the tile is fetched from HBM once and re-read from that L2.
+constexpr int BM = 128, BN = 128;
+constexpr int WK = 32;      // frames per chunk of pw_wgrad_kernel (gemm.hip; one 128-byte line per operand row), the unit in which sep_pw_wgrad (wgrad.hip) bounds nsplit
+
+// One 32-deep chunk of the contraction for a wave's 64x64 tile: 16 k-steps x 4 v_mfma_f32_32x32x2_f32.
+// Operand fragments are fetched from LDS in groups of 4 k-steps, one group ahead of the MFMAs that consume
+// them (two static register sets), so the LDS latency is paid once per chunk instead of once per k-step and
+// the matrix pipe sees 64 back-to-back MFMAs.  A/B are k-major: element (k, i) at base[k*ld + i].
+__device__ __forceinline__ void mfma_chunk32(const float* __restrict__ Ab, const int lda, const float* __restrict__ Bb,
+                                             const int ldb, const int aoff, const int boff, const int lk,
+                                             f32x16& c00, f32x16& c01, f32x16& c10, f32x16& c11) {
+    float fa0[4][2], fb0[4][2], fa1[4][2], fb1[4][2];
+#define SEP_LOAD_FRAGS(FA, FB, g)                                         \
+    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                    \
+        const int ka = 2 * (4 * (g) + ks) + lk;                           \
+        FA[ks][0] = Ab[ka * lda + aoff];                                  \
+        FA[ks][1] = Ab[ka * lda + aoff + 32];                             \
+        FB[ks][0] = Bb[ka * ldb + boff];                                  \
+        FB[ks][1] = Bb[ka * ldb + boff + 32];                             \
+    }
+#define SEP_MFMA_GROUP(FA, FB)                                                            \
+    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                    \
+        c00 = __builtin_amdgcn_mfma_f32_32x32x2f32(FA[ks][0], FB[ks][0], c00, 0, 0, 0);   \
+        c01 = __builtin_amdgcn_mfma_f32_32x32x2f32(FA[ks][0], FB[ks][1], c01, 0, 0, 0);   \
+        c10 = __builtin_amdgcn_mfma_f32_32x32x2f32(FA[ks][1], FB[ks][0], c10, 0, 0, 0);   \
+        c11 = __builtin_amdgcn_mfma_f32_32x32x2f32(FA[ks][1], FB[ks][1], c11, 0, 0, 0);   \
+    }
+    SEP_LOAD_FRAGS(fa0, fb0, 0)
+    SEP_LOAD_FRAGS(fa1, fb1, 1)
+    SEP_MFMA_GROUP(fa0, fb0)
+    SEP_LOAD_FRAGS(fa0, fb0, 2)
+    SEP_MFMA_GROUP(fa1, fb1)
+    SEP_LOAD_FRAGS(fa1, fb1, 3)
+    SEP_MFMA_GROUP(fa0, fb0)
+    SEP_MFMA_GROUP(fa1, fb1)
+#undef SEP_LOAD_FRAGS
+#undef SEP_MFMA_GROUP
+}
+
+// the 8 chunk values of one 32-row (32-column) block -> three packed operands
+__device__ __forceinline__ void split3_frag(const float (&lo4)[4], const float (&hi4)[4], u32x4_t (&out)[3]) {
+    unsigned p[3][4];
+    split3_pair(lo4[0], lo4[1], p[0][0], p[1][0], p[2][0]);
+    split3_pair(lo4[2], lo4[3], p[0][1], p[1][1], p[2][1]);
+    split3_pair(hi4[0], hi4[1], p[0][2], p[1][2], p[2][2]);
+    split3_pair(hi4[2], hi4[3], p[0][3], p[1][3], p[2][3]);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) out[q] = u32x4_t{p[q][0], p[q][1], p[q][2], p[q][3]};
+}
+// acc += A * B on the split operands (6 of the 9 part products)
+__device__ __forceinline__ void mfma_split6(const u32x4_t (&a)[3], const u32x4_t (&b)[3], f32x16& acc) {
+    acc = mfma_bf16(a[0], b[2], acc);
+    acc = mfma_bf16(a[2], b[0], acc);
+    acc = mfma_bf16(a[1], b[1], acc);
+    acc = mfma_bf16(a[0], b[1], acc);
+    acc = mfma_bf16(a[1], b[0], acc);
+    acc = mfma_bf16(a[0], b[0], acc);
 }
 
 }  // namespace

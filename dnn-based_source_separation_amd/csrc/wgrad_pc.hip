@@ -3,7 +3,7 @@
 //   partial[s][m][n] = sum over the (sample, frame) columns of slab s of  G[b][m][t] * pro(X[b][n][t]),   partial_bias[s][m] = sum G
 //
 // Replaces autograd's conv weight / bias gradient of nn.Conv1d(kernel_size=1) at reference src/models/tdcn.py:86,173,175 and
-// src/models/conv_tasnet.py:335,341, like pw_wgrad_split_kernel (gemm.hip), whose arithmetic it keeps: fp32 products from the
+// src/models/conv_tasnet.py:335,341, like pw_wgrad_split_kernel (wgrad.hip), whose arithmetic it keeps: fp32 products from the
 // EXACT three-way bf16 split of both operands (x = hi + mid + lo, 8 + 8 + 8 significand bits; six of the nine part products on
 // v_mfma_f32_32x32x16_bf16, fp32 accumulation) -- both operands are activations here, so there is nothing to pre-split.
 //
@@ -405,7 +405,7 @@ void launch_wpc(const sep_wgrad_desc& d, hipStream_t stream, const char* name) {
 
 }  // namespace
 
-// Called by sep_pw_wgrad (gemm.hip) for the split arithmetics.  Returns 1 when the call was launched here.
+// Called by sep_pw_wgrad (wgrad.hip) for the split arithmetics.  Returns 1 when the call was launched here.
 int sep_pw_wgrad_pc(const sep_wgrad_desc* d, hipStream_t stream) {
     static const bool off = getenv("SEPK_WGRAD_PC") != nullptr && atoi(getenv("SEPK_WGRAD_PC")) == 0;
     const bool tall = d->M % 256 == 0 && d->N % 128 == 0;

@@ -596,7 +596,7 @@ bool w16_accepts(const sep_wgrad_desc* d) {
 
 }  // namespace
 
-// Called by sep_pw_wgrad (gemm.hip) for SEP_ARITH_F16X3.  Returns 1 when the call was launched here (same shapes as sep_pw_wgrad_pc).
+// Called by sep_pw_wgrad (wgrad.hip) for SEP_ARITH_F16X3.  Returns 1 when the call was launched here (same shapes as sep_pw_wgrad_pc).
 int sep_pw_wgrad_pc16(const sep_wgrad_desc* d, hipStream_t stream) {
     if (!w16_accepts(d)) return 0;
     // second G source handed over PRE-SPLIT (sep_split_rows): the heads' [dout; dS] with dS split once per step for all layers.  One 256-row tile
@@ -618,7 +618,7 @@ int sep_pw_wgrad_pc16(const sep_wgrad_desc* d, hipStream_t stream) {
     return 0;
 }
 
-// Called by sep_pw_wgrad_batch (gemm.hip): n products whose descriptors differ in G, G2, X, partial, partial_bias only (the caller has checked
+// Called by sep_pw_wgrad_batch (wgrad.hip): n products whose descriptors differ in G, G2, X, partial, partial_bias only (the caller has checked
 // that).  Returns 1 when they were launched here as ONE grid.
 int sep_pw_wgrad_pc16_batch(const sep_wgrad_desc* ds, int n, hipStream_t stream) {
     if (n < 1 || n > W16_MAXBATCH || !w16_accepts(&ds[0])) return 0;

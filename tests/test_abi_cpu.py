@@ -48,12 +48,15 @@ def test_translation_units_are_listed_once_and_shared_helpers_defined_once():
     csrc = os.path.join(ROOT, "dnn-based_source_separation_amd", "csrc")
     on_disk = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
     assert sorted(entry.HIP_SOURCES) == sorted(f + ".hip" for f in hostsim.FILES) == on_disk
-    assert len(on_disk) == len(set(entry.HIP_SOURCES)) == len(entry.HIP_SOURCES) == len(hostsim.FILES) >= 21
+    assert len(on_disk) == len(set(entry.HIP_SOURCES)) == len(entry.HIP_SOURCES) == len(hostsim.FILES) >= 23
     texts = {f: open(os.path.join(csrc, f)).read() for f in on_disk + ["common.hpp"]}
     defined = {f: re.findall(r'^extern "C" [\w\s\*]*?\b(sep_[a-z0-9_]+)\s*\([^;{]*\)\s*\{', t, flags=re.M) for f, t in texts.items()}
     homes = {n: [f for f, names in defined.items() for m in names if m == n] for n in _declared()}
     assert all(len(h) == 1 for h in homes.values()), {n: h for n, h in homes.items() if len(h) != 1}
     assert defined["runtime.hip"] == ["sep_last_error", "sep_last_kernel", "sep_version"]
+    for n, home in (("sep_pw_gemm", "gemm.hip"), ("sep_pw_wgrad", "wgrad.hip"), ("sep_pw_wgrad_batch", "wgrad.hip"),
+                    ("sep_reduce_slabs", "reduce.hip"), ("sep_f64_to_f32", "reduce.hip")):
+        assert homes[n] == [home], n
     assert re.findall(r"^(?:extern \"C\" )?[\w\s\*]*?\b(\w+)\s*\([^;{]*\)\s*\{", texts["runtime.hip"], flags=re.M) == [
         "sep_set_error", "sep_last_error", "sep_set_kernel", "sep_last_kernel", "sep_version"]
     once = {r"\{\s*return \*reinterpret_cast<const float4\*>\(\w+\);\s*\}": 1,          # a one-line float4 load helper

@@ -77,18 +77,38 @@ def test_the_ledger_lists_every_launch_line_of_the_dispatchers():
         assert text(f).count("SEP_FUSED_COMBOS(") == 1, f
         assert not re.search(r"\(\s*(?:(?:false|true)\s*,\s*)?SEP_PRO_\w+\s*,\s*(?:false|true)\s*,", text(f)), f      # (prologue, two-source, ... spelled out
     assert text("gemm.hip").count("SEP_GEMM_PROLOGUES(") == 1
+    assert text("wgrad.hip").count("SEP_WGRAD_XMODES(") == 2 and "SEP_WGRAD_XMODES(" not in text("gemm.hip")      # the weight gradients' switch: wgrad_split, wgrad_direct
     assert len(GM.INSTANCES) == 28 + 2 * (28 + 3) + (14 * 3 + 2) + 18 + 1
+
+
+def test_the_launch_lines_of_the_products_the_weight_gradients_and_the_reductions_sit_in_their_files():
+    """sep_set_kernel statements per file (a statement inside a launch macro counted once): gemm.hip, wgrad.hip and reduce.hip hold together
+    the eight that the one file they were cut from held, and each of the two fallbacks is named in its own file alone.  The kernel behind
+    "wgrad" stays in gemm.hip beside pw_gemm_kernel (its generated code changes without it) and is launched through sep_pw_wgrad_staged"""
+    import re
+    csrc = os.path.join(ROOT, "dnn-based_source_separation_amd", "csrc")
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".hip")}
+    stmts = {f: re.findall(r"sep_set_kernel\(([^;]*)\);", texts[f]) for f in ("gemm.hip", "wgrad.hip", "reduce.hip")}
+    assert {f: len(s) for f, s in stmts.items()} == {"gemm.hip": 5, "wgrad.hip": 3, "reduce.hip": 0}
+    assert sum(len(s) for s in stmts.values()) == 8
+    assert [s for s in stmts["gemm.hip"] if "#" not in s and "NAME" not in s] == ['"staged"']
+    assert [s for s in stmts["wgrad.hip"] if "#" not in s] == ['"wgrad"']
+    for lit, home in (('"staged"', "gemm.hip"), ('"wgrad"', "wgrad.hip")):
+        assert [f for f, t in texts.items() if lit in t] == [home], lit
+    assert [f for f, t in texts.items() if "void pw_wgrad_kernel(" in t] == [f for f, t in texts.items() if "void pw_gemm_kernel(" in t] == ["gemm.hip"]
+    assert {f: t.count("sep_pw_wgrad_staged(") for f, t in texts.items() if "sep_pw_wgrad_staged(" in t} == {"gemm.hip": 1, "wgrad.hip": 1}
 
 
 def test_the_split_arithmetic_and_the_block_decode_are_spelled_in_one_file():
     """the primitives of SEP_ARITH_F16X3 / SEP_ARITH_BF16X6 (the mixed-precision FMA of the two-part split, the two MFMA builtins, the byte
     selector of the three-part split) and the XCD-aware block decode occur in csrc/gemm_common.hpp and in no other file of csrc/ -- as
     code or as comment --, the float4 load in csrc/common.hpp alone: a second copy under another name would be found here.  The one
-    exception: pw_wgrad_split_kernel and pw_wgrad_direct_kernel (gemm.hip) spell the decode out, once each, because their generated code
-    changes behind the helper -- exactly two occurrences there, so a third copy is still found"""
+    exception: pw_wgrad_split_kernel and pw_wgrad_direct_kernel (wgrad.hip) spell the decode out, once each, because their generated code
+    changes behind the helper -- exactly two occurrences there, so a third copy is still found.  The chunk products that the kernels of
+    gemm.hip and wgrad.hip share are defined in the header and in no .hip file"""
     csrc = os.path.join(ROOT, "dnn-based_source_separation_amd", "csrc")
     texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if os.path.isfile(os.path.join(csrc, f))}
-    assert {"common.hpp", "gemm_common.hpp", "gemm.hip", "gemm_coop.hip", "gemm_pc.hip", "wgrad_pc.hip", "wgrad_pc16.hip", "filterbank.hip", "tcn.hip", "gln.hip", "depthwise.hip", "cln.hip"} <= set(texts)
+    assert {"common.hpp", "gemm_common.hpp", "gemm.hip", "wgrad.hip", "reduce.hip", "gemm_coop.hip", "gemm_pc.hip", "wgrad_pc.hip", "wgrad_pc16.hip", "filterbank.hip", "tcn.hip", "gln.hip", "depthwise.hip", "cln.hip"} <= set(texts)
     once = {"v_fma_mix_f32": "gemm_common.hpp",
             "__builtin_amdgcn_mfma_f32_32x32x16_f16(": "gemm_common.hpp",
             "__builtin_amdgcn_mfma_f32_32x32x16_bf16(": "gemm_common.hpp",
@@ -96,10 +116,12 @@ def test_the_split_arithmetic_and_the_block_decode_are_spelled_in_one_file():
             "float4 ld4(": "common.hpp"}
     for spelling, home in once.items():
         assert [f for f, t in texts.items() if spelling in t] == [home], spelling
-    assert {f: t.count("bid & 7") for f, t in texts.items() if "bid & 7" in t} == {"gemm_common.hpp": 1, "gemm.hip": 2}
+    assert {f: t.count("bid & 7") for f, t in texts.items() if "bid & 7" in t} == {"gemm_common.hpp": 1, "wgrad.hip": 2}
     for kernel in ("pw_wgrad_direct_kernel", "pw_wgrad_split_kernel"):          # ... and the two are where they are said to be
-        body = texts["gemm.hip"].split("void %s(const sep_wgrad_desc d) {" % kernel)[1]
+        body = texts["wgrad.hip"].split("void %s(const sep_wgrad_desc d) {" % kernel)[1]
         assert "bid & 7" in body[:body.index("__syncthreads()")], kernel
+    for helper in ("mfma_chunk32(", "split3_frag(", "mfma_split6("):
+        assert [f for f, t in texts.items() if "void " + helper in t] == ["gemm_common.hpp"], helper
 
 
 def _one_case(sim_library, perturb):

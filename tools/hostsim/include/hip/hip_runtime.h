@@ -209,7 +209,7 @@ static void sim_launch(K kernel, dim3 grid, dim3 block, size_t shmem, A... args)
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) sim_launch(kernel, dim3(grid), dim3(block), (size_t)(shmem), __VA_ARGS__)
 
 // =====================================================================================================================================
-// The GEMM files (gemm.hip, gemm_coop.hip, gemm_pc.hip, wgrad_pc.hip) use more of the machine: LDS-DMA, DPP, byte permutes, packed
+// The GEMM files (gemm.hip, wgrad.hip, gemm_coop.hip, gemm_pc.hip, wgrad_pc.hip) use more of the machine: LDS-DMA, DPP, byte permutes, packed
 // conversions, the 32x32 MFMA shapes, hand-placed waits.  tools/hostsim.py rewrites a few helper bodies in the copies it compiles
 // (the inline-assembly ones); everything else is restated here.  LDS-DMA lands immediately (the hardware's asynchrony is not modelled:
 // waits are no-ops), LDS byte addresses are offsets from an anchor object of the library.
