@@ -76,6 +76,7 @@ const seq_entry SEQ_TABLE[] = {
     SEQ_FN(sep_stitch_cost), SEQ_FN(sep_stitch_chain), SEQ_FN(sep_stitch_ola),
     SEQ_FN(sep_resample_fwd), SEQ_FN(sep_resample_stream_fwd),
     SEQ_FN(sep_mix_draw), SEQ_FN(sep_mix_render),
+    SEQ_FN(sep_mix_draw_speed), SEQ_FN(sep_mix_render_speed),
 };
 constexpr int SEQ_COUNT = (int)(sizeof(SEQ_TABLE) / sizeof(SEQ_TABLE[0]));
 

@@ -19,7 +19,9 @@ sisdr: negative SI-SDR).  Validation scores mixtures of mixtures of the validati
 `--dynamic_mixing 1` trains on fresh mixtures every step (sepkernels.mixing.DynamicMixer): the utterances behind `--train_list_path` (its s1 .. sn
 files, each kept once; recipes.dynamic_mixing.corpus_from_mix_list) are decoded once and kept on the device, and every step draws new speakers,
 crops and gains there -- `--dm_gain_db G` (default 2.5: gains uniform in [-G, G] dB around the common level), `--dm_steps_per_epoch N` (default:
-the length of the fixed loader it replaces), `--dm_seed S` (default: --seed).  Validation stays on the fixed list.  Not with --criterion mixit.
+the length of the fixed loader it replaces), `--dm_seed S` (default: --seed), `--dm_speeds 95,100,105` (default: none; speed perturbation of
+every source before it is mixed -- integer percentages in 50 .. 200, resampled on the device inside the render kernel; the level is not
+renormalised and a noise row is never perturbed).  Validation stays on the fixed list.  Not with --criterion mixit.
 """
 import argparse
 import os
@@ -89,6 +91,7 @@ def build_parser():
     ap.add_argument("--dm_gain_db", type=float, default=2.5, help="with --dynamic_mixing: gains are drawn from [-G, G] dB")
     ap.add_argument("--dm_steps_per_epoch", type=int, default=None, help="with --dynamic_mixing: steps per epoch (default: the length of the fixed loader)")
     ap.add_argument("--dm_seed", type=int, default=None, help="with --dynamic_mixing: the seed of the draw (default: --seed)")
+    ap.add_argument("--dm_speeds", type=str, default=None, help="with --dynamic_mixing: speed perturbation, integer percentages such as 95,100,105 (default: none)")
     return ap
 
 
@@ -153,7 +156,10 @@ def main(argv=None):
                                                                                        corpus.samples.numel() * corpus.samples.element_size() / 1e6, dev))
         args.dynamic_mixer = DynamicMixer(corpus, n_sources=args.n_sources, samples=samples, batch_size=args.batch_size,
                                           seed=args.seed if args.dm_seed is None else args.dm_seed, gain_db=(-abs(args.dm_gain_db), abs(args.dm_gain_db)),
-                                          gain_steps=256 if args.dm_gain_db else 1, rank=rank, world=world)
+                                          gain_steps=256 if args.dm_gain_db else 1, rank=rank, world=world,
+                                          speeds=None if not args.dm_speeds else [float(P) for P in args.dm_speeds.split(",")])
+        if rank == 0 and args.dm_speeds:
+            print("Speed perturbation: {} percent.".format(", ".join(str(P) for P in args.dynamic_mixer.speeds)))
         args.dynamic_steps_per_epoch = args.dm_steps_per_epoch
 
     stride = args.kernel_size // 2 if args.stride is None else args.stride

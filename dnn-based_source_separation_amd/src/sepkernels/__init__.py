@@ -23,6 +23,7 @@ STATS_SLOTS = 16   # SEP_STATS_SLOTS: gLN statistics are double[B][STATS_SLOTS][
 ARRIVE_INTS = 17   # SEP_ARRIVE_INTS: arrival counters of the gLN-backward publishers, int[B][ARRIVE_INTS]
 ARITH_F32, ARITH_BF16X6, ARITH_F16X3 = 0, 1, 2     # SEP_ARITH_*: how sep_pw_gemm forms its fp32 products (include/sepkernels.h)
 MIX_MAX_SOURCES, MIX_GUARD, MIX_INT16, MIX_F32 = 8, 16, 0, 1      # SEP_MIX_*: what sep_mix_draw / sep_mix_render take, the corpus's guard zeros, its sample kinds
+MIX_MAX_SPEEDS, MIX_SPEED_MIN, MIX_SPEED_MAX, MIX_SPEED_MAX_TAPS, MIX_SPEED_DESC = 16, 50, 200, 32, 8      # SEP_MIX_*SPEED*: speed perturbation in sep_mix_draw_speed / sep_mix_render_speed
 MIXIT_SLAB = 2048  # SEP_MIXIT_SLAB: samples behind one partial sum of sep_mixit_gram
 MIXIT_MAX_EST, MIXIT_MAX_MIX, MIXIT_MAX_CODES = 16, 8, 65536       # SEP_MIXIT_MAX_*: what sep_mixit_search takes
 PAIR_SLAB = 2048   # SEP_PAIR_SLAB: samples behind one partial sum of sep_pair_gram
@@ -265,6 +266,9 @@ SIGNATURES = {
     # dynamic mixing from a device-resident corpus (ABI 23, additive): the plan of a batch from a step count in device memory, the gather-scale-sum pass
     "sep_mix_draw": [_vp, _vp, _I, _I, _vp, _I, _vp, _vp, _I, _vp, _vp, _I, _vp, _L, _L, _L, _I, _I, _I, _vp, _vp, _vp],
     "sep_mix_render": [_vp, _I, _vp, _I, _vp, _vp, _I, _vp, _vp, _I, _I, _I, _vp, _vp, _vp, _vp],
+    # ... with speed perturbation (ABI 23, additive): the twins of the two above with speed descriptors, a speed index per row and the filter buffers
+    "sep_mix_draw_speed": [_vp, _vp, _I, _I, _vp, _I, _vp, _vp, _I, _vp, _vp, _I, _vp, _L, _L, _L, _I, _I, _I, _vp, _I, _vp, _vp, _vp, _vp],
+    "sep_mix_render_speed": [_vp, _I, _vp, _I, _vp, _vp, _I, _vp, _vp, _vp, _vp, _I, _vp, _L, _vp, _L, _I, _I, _I, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"sep_last_error": ctypes.c_char_p, "sep_last_kernel": ctypes.c_char_p, "sep_seq_name": ctypes.c_char_p, "sep_cln_ws_bytes": ctypes.c_size_t,
              "sep_gln_tokens_ws_bytes": ctypes.c_size_t, "sep_online_state_row_bytes": ctypes.c_size_t, "sep_bss_scratch_bytes": ctypes.c_size_t, "sep_bss_image_scratch_bytes": ctypes.c_size_t,
@@ -1021,6 +1025,27 @@ class HipBackend:
         _check(load().sep_mix_render(_ptr(samples), kind, _ptr(offsets, torch.int64), U, _ptr(noise_samples), _ptr(noise_offsets, torch.int64), U_noise,
                                      _ptr(plan, torch.int64), _ptr(gain, _f32), B, n, T, _ptr(sources, _f32), _ptr(mixture, _f32), _ptr(noise, _f32), _stream()),
                "sep_mix_render")
+
+    # ... with speed perturbation: desc (J, MIX_SPEED_DESC) int32, speed (B, R) int32, filter_table fp32 and filter_first int32 (every speed's, one behind the other)
+    def mix_draw_speed(self, offsets, spk_first, U, S, noise_offsets, U_noise, level, gain_table, G, noise_level, noise_gain_table, G_noise, counter, seed,
+                       item_stride, item_first, B, n, T, desc, J, plan, gain, speed):
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        _check(load().sep_mix_draw_speed(_ptr(offsets, torch.int64), _ptr(spk_first, torch.int32), U, S, _ptr(noise_offsets, torch.int64), U_noise, _ptr(level, _f32),
+                                         _ptr(gain_table, _f32), G, _ptr(noise_level, _f32), _ptr(noise_gain_table, _f32), G_noise, _ptr(counter, torch.int64),
+                                         seed - (1 << 64) if seed >> 63 else seed, item_stride, item_first, B, n, T, _ptr(desc, torch.int32), J, _ptr(plan, torch.int64),
+                                         _ptr(gain, _f32), _ptr(speed, torch.int32), _stream()),
+               "sep_mix_draw_speed")
+
+    def mix_render_speed(self, samples, offsets, U, noise_samples, noise_offsets, U_noise, plan, gain, speed, desc, J, filter_table, filter_first, B, n, T, sources,
+                         mixture, noise):
+        kind = {torch.int16: MIX_INT16, torch.float32: MIX_F32}.get(samples.dtype)
+        if kind is None or (noise_samples is not None and noise_samples.dtype != samples.dtype):
+            raise SepKernelsError("mix_render_speed takes int16 or float32 samples, the noise corpus of the same kind")
+        _check(load().sep_mix_render_speed(_ptr(samples), kind, _ptr(offsets, torch.int64), U, _ptr(noise_samples), _ptr(noise_offsets, torch.int64), U_noise,
+                                           _ptr(plan, torch.int64), _ptr(gain, _f32), _ptr(speed, torch.int32), _ptr(desc, torch.int32), J, _ptr(filter_table, _f32),
+                                           filter_table.numel(), _ptr(filter_first, torch.int32), filter_first.numel(), B, n, T, _ptr(sources, _f32),
+                                           _ptr(mixture, _f32), _ptr(noise, _f32), _stream()),
+               "sep_mix_render_speed")
 
 
 _backend = HipBackend()

@@ -18,11 +18,25 @@ The draw (include/sepkernels.h states it in full; tests/test_dynamic_mixing_gpu.
 so the global batch of a step is the same set of mixtures however it is cut into ranks.  Gains come from a table of `gain_steps` entries between
 gain_db[0] and gain_db[1], built here in fp64: nothing transcendental runs on the device and the plan is reproducible bit for bit.
 
-Routes.  A corpus on the GPU runs csrc/mixing.hip (sep_mix_draw, sep_mix_render).  A corpus on the CPU -- and any backend without the two methods --
-runs the same definitions composed in numpy uint64 and torch; both give the same plan and the same bits.
+Speed perturbation (speeds=(95, 100, 105); include/sepkernels.h states it in full).  Every source also draws one of J integer percentages P
+(50 .. 200, at most 16, distinct), j = below(word(.., 4 n + 3 + i), J), and is resampled from rate P to rate 100 before it is cropped: tempo and
+pitch move together, P > 100 is shorter and higher (sox `speed`), P = 100 is the plain copy.  The filter is sepkernels.resample.get_filter(P, 100)
+in its compact form; with g = gcd(P, 100), o = P / g, u = 100 / g the perturbed utterance has len' = ceil(u len / o) samples,
+    v[i u + p] = (float)(sum over k < Kc, ascending, in fp64, of (double)table[k][p] * (double)x[i o + first[p] + k - width])
+with x the RAW sample (the int16 integer or the fp32 value), zero outside its own utterance, and a row is gain * (v[start + t - lead] * scale) under
+the predicate of the plain render with len' in place of len; the position is drawn from len'.  Every product is exact in fp64, so the kernels, numpy
+and the host simulation give the same bits.  The level is NOT renormalised after the perturbation (gain = level[u] * gain_table[g] as before: the
+RMS of a perturbed utterance differs from the original's by the filter's pass band, about 1e-3), and the noise row is never perturbed.
 
-Not offered: speed perturbation, peak normalisation of the mixture, mixtures of mixtures, a multi-channel corpus.
+Routes.  A corpus on the GPU runs csrc/mixing.hip (sep_mix_draw, sep_mix_render; with speeds sep_mix_draw_speed, sep_mix_render_speed).  A corpus on
+the CPU -- and any backend without the two methods -- runs the same definitions composed in numpy (uint64 for the draw, an fp64 loop over the taps
+for a perturbed row) and torch; both give the same plan and the same bits.
+
+Not offered: perturbing the noise row, non-integer percentages, renormalising the level after the perturbation, peak normalisation of the mixture,
+mixtures of mixtures, a multi-channel corpus.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -30,6 +44,7 @@ import sepkernels
 
 GUARD = sepkernels.MIX_GUARD
 MAX_SOURCES = sepkernels.MIX_MAX_SOURCES
+MAX_SPEEDS, SPEED_MIN, SPEED_MAX = sepkernels.MIX_MAX_SPEEDS, sepkernels.MIX_SPEED_MIN, sepkernels.MIX_SPEED_MAX
 DEFAULT_REF_RMS = 10.0 ** (-25.0 / 20.0)          # -25 dB re full scale, the figure wsj0-mix's scripts normalise the (active) level to
 _GOLD, _M1, _M2 = np.uint64(0x9E3779B97F4A7C15), np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB)
 _MASK = (1 << 64) - 1
@@ -206,9 +221,9 @@ class DeviceCorpus:
 
 
 # ---- the composed route: the definitions of include/sepkernels.h in numpy uint64 and torch --------------------------------------------------------
-def _place(key, k_pos, k_gain, u, lengths, T, G):
-    """-> start, lead, gain index (int64 arrays) of rows whose utterances are u"""
-    ln = lengths[u].astype(np.int64)
+def _place(key, k_pos, k_gain, u, lengths, T, G, ln=None):
+    """-> start, lead, gain index (int64 arrays) of rows whose utterances are u (ln: the rows' own lengths where they are not the utterances')"""
+    ln = lengths[u].astype(np.int64) if ln is None else ln
     w = _mix64(key + np.uint64(k_pos))
     long_ = ln >= T
     start = np.where(long_, _below(w, np.where(long_, ln - T + 1, 1)), 0).astype(np.int64)
@@ -217,8 +232,65 @@ def _place(key, k_pos, k_gain, u, lengths, T, G):
     return start, lead, g
 
 
-def draw_composed(corpus, noise, table, noise_table, seed, step, item_stride, item_first, B, n, T):
-    """-> plan (B, R, 4) int64 and gain (B, R) float32, on the CPU: what sep_mix_draw writes for step `step`"""
+def check_speeds(speeds):
+    """-> the speeds as a tuple of ints; ValueError for anything sep_mix_draw_speed does not take"""
+    try:
+        given = list(speeds)
+    except TypeError:
+        raise ValueError("speeds is a list of integer percentages, given {!r}".format(speeds))
+    if len(given) < 1:
+        raise ValueError("speeds is empty: at least one percentage (None switches speed perturbation off)")
+    if len(given) > MAX_SPEEDS:
+        raise ValueError("{} speeds, at most {}".format(len(given), MAX_SPEEDS))
+    out = []
+    for P in given:
+        if isinstance(P, bool) or not isinstance(P, (int, float, np.integer, np.floating)) or not math.isfinite(P) or int(P) != P:
+            raise ValueError("a speed is an integer percentage, given {!r}".format(P))
+        if not SPEED_MIN <= int(P) <= SPEED_MAX:
+            raise ValueError("a speed lies in [{}, {}] percent, given {}".format(SPEED_MIN, SPEED_MAX, int(P)))
+        out.append(int(P))
+    if len(set(out)) != len(out):
+        raise ValueError("duplicate speeds in {}".format(out))
+    return tuple(out)
+
+
+class SpeedFilters:
+    """the filters of a list of speeds as sep_mix_render_speed takes them: desc (J, 8) int32 {o, u, width, Kc, table offset, first offset, P, 0},
+    table fp32 and first int32 of every speed one behind the other (host tensors; an identity speed has no filter)"""
+
+    def __init__(self, speeds):
+        from sepkernels.resample import get_filter
+        self.speeds = check_speeds(speeds)
+        desc, tables, firsts, self.filters = [], [], [], []
+        toff = foff = 0
+        for P in self.speeds:
+            if P == 100:
+                desc.append([1, 1, 0, 1, 0, 0, 100, 0])
+                self.filters.append(None)
+                continue
+            f = get_filter(P, 100)
+            if f.Kc > sepkernels.MIX_SPEED_MAX_TAPS or f.u > 100 or f.o > SPEED_MAX:
+                raise ValueError("the filter of speed {} has {} taps of {} phases: beyond what the kernels take".format(P, f.Kc, f.u))
+            desc.append([f.o, f.u, f.width, f.Kc, toff, foff, P, 0])
+            tables.append(f.table.reshape(-1))
+            firsts.append(f.first.reshape(-1))
+            toff, foff = toff + f.Kc * f.u, foff + f.u
+            self.filters.append(f)
+        self.desc = torch.tensor(desc, dtype=torch.int32)
+        self.table = torch.cat(tables).contiguous() if tables else torch.zeros(1, dtype=torch.float32)
+        self.first = torch.cat(firsts).to(torch.int32).contiguous() if firsts else torch.zeros(1, dtype=torch.int32)
+
+    def length(self, j, length):
+        """len' of an utterance of `length` samples at speed j"""
+        o, u = int(self.desc[j, 0]), int(self.desc[j, 1])
+        return min(max((u * int(length) + o - 1) // o, 1), (1 << 31) - 1)
+
+
+def draw_composed(corpus, noise, table, noise_table, seed, step, item_stride, item_first, B, n, T, speeds=None):
+    """-> plan (B, R, 4) int64 and gain (B, R) float32, on the CPU: what sep_mix_draw writes for step `step`; with speeds (a list of percentages or a
+    SpeedFilters) also speed (B, R) int32: what sep_mix_draw_speed writes"""
+    if speeds is not None and not isinstance(speeds, SpeedFilters):
+        speeds = SpeedFilters(speeds)
     first = (int(step) * int(item_stride) + int(item_first)) & _MASK
     item = np.array([(first + b) & _MASK for b in range(B)], dtype=np.uint64)
     with np.errstate(over="ignore"):
@@ -226,6 +298,7 @@ def draw_composed(corpus, noise, table, noise_table, seed, step, item_stride, it
         S, spk, lengths = corpus.num_speakers, corpus.spk_first_host, corpus.offsets_host[1:] - corpus.offsets_host[:-1]
         R = n + (1 if noise is not None else 0)
         plan = np.zeros((B, R, 4), dtype=np.int64)
+        speed = np.full((B, R), -1, dtype=np.int32)
         taken = np.zeros((B, 0), dtype=np.int64)                    # ascending per item
         for i in range(n):
             r = _below(_mix64(key + np.uint64(i)), S - i).astype(np.int64)
@@ -233,7 +306,13 @@ def draw_composed(corpus, noise, table, noise_table, seed, step, item_stride, it
                 r = r + (r >= taken[:, c])
             taken = np.sort(np.concatenate([taken, r[:, None]], axis=1), axis=1)
             u = spk[r] + _below(_mix64(key + np.uint64(n + i)), spk[r + 1] - spk[r]).astype(np.int64)
-            start, lead, g = _place(key, 2 * n + i, 3 * n + i, u, lengths, T, table.numel())
+            ln = None
+            if speeds is not None:
+                j = _below(_mix64(key + np.uint64(4 * n + 3 + i)), len(speeds.speeds)).astype(np.int64)
+                speed[:, i] = j
+                o, up = speeds.desc[:, 0].numpy().astype(np.int64)[j], speeds.desc[:, 1].numpy().astype(np.int64)[j]
+                ln = np.clip((up * lengths[u].astype(np.int64) + o - 1) // o, 1, (1 << 31) - 1)          # len' of every row
+            start, lead, g = _place(key, 2 * n + i, 3 * n + i, u, lengths, T, table.numel(), ln)
             plan[:, i] = np.stack([u, start, lead, g], axis=1)
         if noise is not None:
             nl = noise.offsets_host[1:] - noise.offsets_host[:-1]
@@ -244,6 +323,8 @@ def draw_composed(corpus, noise, table, noise_table, seed, step, item_stride, it
     gain = corpus.level.detach().cpu()[plan[:, :n, 0]] * table.cpu()[plan[:, :n, 3]]
     if noise is not None:
         gain = torch.cat([gain, noise.level.detach().cpu()[plan[:, n:, 0]] * noise_table.cpu()[plan[:, n:, 3]]], dim=1)
+    if speeds is not None:
+        return plan, gain.contiguous(), torch.from_numpy(speed)
     return plan, gain.contiguous()
 
 
@@ -262,13 +343,56 @@ def _render_row(corpus, row, g, T):
     return torch.where(inside, val, torch.zeros_like(val))
 
 
-def render_composed(corpus, noise, plan, gain, n, T):
-    """-> sources (B, n, T), mixture (B, 1, T)[, noise (B, 1, T)] float32 on the corpus's device: what sep_mix_render writes for this plan"""
+def _render_row_speed(corpus, row, g, T, flt):
+    """one perturbed row: the formula of sep_mix_render_speed with its clamps and its predicate, the taps summed in fp64 in numpy"""
+    U = corpus.num_utterances
+    uu = min(max(int(row[0]), 0), U - 1)
+    o0, ln = int(corpus.offsets_host[uu]), int(corpus.offsets_host[uu + 1] - corpus.offsets_host[uu])
+    o, u, width, Kc = flt.o, flt.u, flt.width, flt.Kc
+    lenp = min(max((u * ln + o - 1) // o, 1), (1 << 31) - 1)
+    start = max(min(int(row[1]), lenp - 1), 0)
+    lead = min(max(int(row[2]), -(1 << 40)), 1 << 40)
+    t = np.arange(T, dtype=np.int64)
+    inside = (t >= lead) & (t - lead < lenp - start)
+    m = np.where(inside, start + t - lead, 0)
+    i, p = m // u, m % u
+    x = corpus.samples[o0:o0 + ln].detach().cpu().numpy().astype(np.float64)
+    table, first = flt.table.numpy(), flt.first.numpy().astype(np.int64)
+    acc = np.zeros(T, dtype=np.float64)
+    for k in range(Kc):
+        idx = i * o + first[p] + k - width
+        ok = (idx >= 0) & (idx < ln)
+        acc = acc + table[k, p].astype(np.float64) * np.where(ok, x[np.clip(idx, 0, ln - 1)], 0.0)
+    v = torch.from_numpy(acc.astype(np.float32)).to(corpus.device)
+    scale = 2.0 ** -15 if corpus.dtype == torch.int16 else 1.0
+    val = g * (v * scale)
+    return torch.where(torch.from_numpy(inside).to(corpus.device), val, torch.zeros_like(val))
+
+
+def render_composed(corpus, noise, plan, gain, n, T, speeds=None, speed=None):
+    """-> sources (B, n, T), mixture (B, 1, T)[, noise (B, 1, T)] float32 on the corpus's device: what sep_mix_render writes for this plan; with speeds
+    (a list of percentages or a SpeedFilters) and speed (B, R): what sep_mix_render_speed writes"""
     B, R = plan.shape[0], plan.shape[1]
+    if (speeds is None) != (speed is None):
+        raise ValueError("speeds and the speed indices of a plan come together or not at all")
+    if speeds is not None:
+        if not isinstance(speeds, SpeedFilters):
+            speeds = SpeedFilters(speeds)
+        if tuple(speed.shape) != (B, R):
+            raise ValueError("the speed indices of a plan of {} rows per item are ({}, {}), given {}".format(R, B, R, tuple(speed.shape)))
+        picks, J = speed.detach().cpu().tolist(), len(speeds.speeds)
+
+        def one(b, i, g):
+            j = min(max(picks[b][i], -1), J - 1)
+            flt = speeds.filters[j] if j >= 0 else None
+            return _render_row(corpus, rows[b][i], g, T) if flt is None else _render_row_speed(corpus, rows[b][i], g, T, flt)
+    else:
+        def one(b, i, g):
+            return _render_row(corpus, rows[b][i], g, T)
     if R != n + (1 if noise is not None else 0):
         raise ValueError("the plan has {} rows per item, {} sources{} need {}".format(R, n, " and a noise row" if noise is not None else "", n + (noise is not None)))
     rows, gains = plan.detach().cpu().tolist(), gain.detach().to(corpus.device, torch.float32)
-    sources = torch.stack([torch.stack([_render_row(corpus, rows[b][i], gains[b, i], T) for i in range(n)]) for b in range(B)])
+    sources = torch.stack([torch.stack([one(b, i, gains[b, i]) for i in range(n)]) for b in range(B)])
     mixture = sources[:, 0]
     for i in range(1, n):
         mixture = mixture + sources[:, i]
@@ -283,10 +407,12 @@ class DynamicMixer:
     """mixer = DynamicMixer(corpus, n_sources=2, samples=32000, batch_size=16, seed=111)
     mixture, sources = mixer()            # (B, 1, T), (B, n, T) float32 on the corpus's device; with noise=...: (mixture, sources, noise)
     mixer.plan                            # the last draw: ((B, R, 4) int64 {utterance, start, lead, gain index}, (B, R) gains), for logging and render()
-    mixer.step, mixer.seek(step), mixer.state_dict(), mixer.load_state_dict(...)      # {seed, step}: a resumed run continues the stream"""
+    mixer.step, mixer.seek(step), mixer.state_dict(), mixer.load_state_dict(...)      # {seed, step}: a resumed run continues the stream
+    DynamicMixer(..., speeds=(95, 100, 105))      # speed perturbation of every source (the module's docstring): draw() -> (plan, gain, speed),
+    mixer.speed                                   # (B, R) int32, the index into speeds per row (-1: the noise row); render(plan, gain, speed)"""
 
     def __init__(self, corpus, n_sources=2, samples=32000, batch_size=16, seed=111, gain_db=(-2.5, 2.5), gain_steps=256, noise=None,
-                 noise_gain_db=(-6.0, 3.0), rank=None, world=None, composed=False):
+                 noise_gain_db=(-6.0, 3.0), rank=None, world=None, composed=False, speeds=None):
         """rank / world default to torch.distributed's when it is initialised (else 0 of 1); composed=True keeps a mixer off the kernels (the composed
         route on whatever device the corpus is on: the same plan and the same bits)"""
         n, T, B = int(n_sources), int(samples), int(batch_size)
@@ -298,6 +424,7 @@ class DynamicMixer:
             raise ValueError("samples must be in [1, 2^31), given {}".format(T))
         if B < 1 or B > 65535:
             raise ValueError("batch_size must be in [1, 65535], given {}".format(B))
+        filters = SpeedFilters(speeds) if speeds is not None else None          # (its ValueErrors come before anything is uploaded)
         if noise is not None:
             if noise.dtype != corpus.dtype:
                 raise ValueError("the noise corpus holds {}, the corpus {}: one sample kind".format(noise.dtype, corpus.dtype))
@@ -319,6 +446,9 @@ class DynamicMixer:
         self._step = 0
         self._counter = torch.zeros(1, dtype=torch.int64, device=dev)      # the step as the draw kernel reads and advances it
         self.plan = None
+        self.speeds, self.speed, self._filters = (filters.speeds if filters else None), None, filters
+        if filters is not None:
+            self._desc, self._ftable, self._ffirst = filters.desc.to(dev), filters.table.to(dev), filters.first.to(dev)
 
     @property
     def rows(self):
@@ -328,7 +458,8 @@ class DynamicMixer:
         K = sepkernels.backend()
         if self.composed:
             return False
-        return self.corpus.samples.is_cuda or (K.name != "hip" and hasattr(K, "mix_draw") and hasattr(K, "mix_render"))
+        names = ("mix_draw", "mix_render") if self.speeds is None else ("mix_draw_speed", "mix_render_speed")
+        return self.corpus.samples.is_cuda or (K.name != "hip" and all(hasattr(K, name) for name in names))
 
     @property
     def step(self):
@@ -340,46 +471,70 @@ class DynamicMixer:
         self._counter.fill_(self._step)
 
     def state_dict(self):
-        return {"seed": self.seed, "step": self._step}
+        state = {"seed": self.seed, "step": self._step}
+        if self.speeds is not None:
+            state["speeds"] = list(self.speeds)
+        return state
 
     def load_state_dict(self, state):
+        theirs = state.get("speeds")
+        if (None if theirs is None else tuple(int(P) for P in theirs)) != self.speeds:
+            raise ValueError("the state was written with speeds {}, this mixer has {}: the stream would differ".format(theirs, self.speeds))
         self.seed = int(state["seed"]) & _MASK
         self.seek(int(state["step"]))
 
     def draw(self):
-        """-> (plan, gain) of this step on the corpus's device; advances the step"""
+        """-> (plan, gain) of this step on the corpus's device -- with speeds (plan, gain, speed); advances the step"""
         c, nz, B, n, T = self.corpus, self.noise, self.batch_size, self.n_sources, self.samples
         stride, first = B * self.world, self.rank * B
+        speed = None
         if self._on_kernels():
             plan = torch.empty(B, self.rows, 4, dtype=torch.int64, device=c.device)
             gain = torch.empty(B, self.rows, dtype=torch.float32, device=c.device)
-            sepkernels.backend().mix_draw(c.offsets, c.spk_first, c.num_utterances, c.num_speakers, None if nz is None else nz.offsets,
-                                          0 if nz is None else nz.num_utterances, c.level, self.gain_table, self.gain_table.numel(),
-                                          None if nz is None else nz.level, self.noise_gain_table, 0 if nz is None else self.noise_gain_table.numel(),
-                                          self._counter, self.seed, stride, first, B, n, T, plan, gain)
+            if self.speeds is not None:
+                speed = torch.empty(B, self.rows, dtype=torch.int32, device=c.device)
+                sepkernels.backend().mix_draw_speed(c.offsets, c.spk_first, c.num_utterances, c.num_speakers, None if nz is None else nz.offsets,
+                                                    0 if nz is None else nz.num_utterances, c.level, self.gain_table, self.gain_table.numel(),
+                                                    None if nz is None else nz.level, self.noise_gain_table, 0 if nz is None else self.noise_gain_table.numel(),
+                                                    self._counter, self.seed, stride, first, B, n, T, self._desc, len(self.speeds), plan, gain, speed)
+            else:
+                sepkernels.backend().mix_draw(c.offsets, c.spk_first, c.num_utterances, c.num_speakers, None if nz is None else nz.offsets,
+                                              0 if nz is None else nz.num_utterances, c.level, self.gain_table, self.gain_table.numel(),
+                                              None if nz is None else nz.level, self.noise_gain_table, 0 if nz is None else self.noise_gain_table.numel(),
+                                              self._counter, self.seed, stride, first, B, n, T, plan, gain)
         else:
-            plan, gain = draw_composed(c, nz, self.gain_table, self.noise_gain_table, self.seed, self._step, stride, first, B, n, T)
-            plan, gain = plan.to(c.device), gain.to(c.device)
+            out = draw_composed(c, nz, self.gain_table, self.noise_gain_table, self.seed, self._step, stride, first, B, n, T, speeds=self._filters)
+            plan, gain = out[0].to(c.device), out[1].to(c.device)
+            speed = out[2].to(c.device) if self.speeds is not None else None
             self._counter += 1
         self._step += 1
-        self.plan = (plan, gain)
-        return plan, gain
+        self.plan, self.speed = (plan, gain), speed
+        return (plan, gain) if self.speeds is None else (plan, gain, speed)
 
-    def render(self, plan, gain):
-        """-> (mixture, sources[, noise]) of a plan (this mixer's or a logged one)"""
+    def render(self, plan, gain, speed=None):
+        """-> (mixture, sources[, noise]) of a plan (this mixer's or a logged one); a mixer with speeds takes the plan's speed indices too"""
         c, nz, n, T = self.corpus, self.noise, self.n_sources, self.samples
         B = plan.shape[0]
         if tuple(plan.shape) != (B, self.rows, 4) or tuple(gain.shape) != (B, self.rows) or B < 1:
             raise ValueError("a plan is (B, {}, 4) int64 with gains (B, {}), given {} and {}".format(self.rows, self.rows, tuple(plan.shape), tuple(gain.shape)))
+        if (speed is None) != (self.speeds is None) or (speed is not None and tuple(speed.shape) != (B, self.rows)):
+            raise ValueError("a mixer with speeds renders (plan, gain, speed) with speed ({}, {}) int32, one without renders (plan, gain); given speed {}".format(
+                B, self.rows, None if speed is None else tuple(speed.shape)))
         if self._on_kernels():
             sources = torch.empty(B, n, T, dtype=torch.float32, device=c.device)
             mixture = torch.empty(B, 1, T, dtype=torch.float32, device=c.device)
             extra = torch.empty(B, 1, T, dtype=torch.float32, device=c.device) if nz is not None else None
+            if self.speeds is not None:
+                sepkernels.backend().mix_render_speed(c.samples, c.offsets, c.num_utterances, None if nz is None else nz.samples, None if nz is None else nz.offsets,
+                                                      0 if nz is None else nz.num_utterances, plan.to(torch.int64).contiguous(), gain.to(torch.float32).contiguous(),
+                                                      speed.to(c.device, torch.int32).contiguous(), self._desc, len(self.speeds), self._ftable, self._ffirst, B, n, T,
+                                                      sources, mixture, extra)
+                return (mixture, sources) if nz is None else (mixture, sources, extra)
             sepkernels.backend().mix_render(c.samples, c.offsets, c.num_utterances, None if nz is None else nz.samples, None if nz is None else nz.offsets,
                                             0 if nz is None else nz.num_utterances, plan.to(torch.int64).contiguous(), gain.to(torch.float32).contiguous(), B, n, T,
                                             sources, mixture, extra)
             return (mixture, sources) if nz is None else (mixture, sources, extra)
-        out = render_composed(c, nz, plan, gain, n, T)
+        out = render_composed(c, nz, plan, gain, n, T, speeds=self._filters, speed=speed)
         return (out[1], out[0]) if nz is None else (out[1], out[0], out[2])
 
     def __call__(self):
@@ -387,4 +542,5 @@ class DynamicMixer:
             return self.render(*self.draw())
 
 
-__all__ = ["DeviceCorpus", "DynamicMixer", "gain_table", "draw_composed", "render_composed", "GUARD", "MAX_SOURCES", "DEFAULT_REF_RMS"]
+__all__ = ["DeviceCorpus", "DynamicMixer", "SpeedFilters", "check_speeds", "gain_table", "draw_composed", "render_composed", "GUARD", "MAX_SOURCES", "MAX_SPEEDS",
+           "SPEED_MIN", "SPEED_MAX", "DEFAULT_REF_RMS"]

@@ -1029,6 +1029,62 @@ int sep_mix_draw(const int64_t* offsets, const int32_t* spk_first, int U, int S,
 int sep_mix_render(const void* samples, int kind, const int64_t* offsets, int U, const void* noise_samples, const int64_t* noise_offsets, int U_noise,
                    const int64_t* plan, const float* gain, int B, int n, int T, float* sources, float* mixture, float* noise, sep_stream_t stream);
 
+/* ---- Speed perturbation in dynamic mixing (ABI 23, additive; csrc/mixing.hip, sepkernels/mixing.py) ----------------------------------------------
+ * Every source of a drawn mixture is resampled by a few percent before it is cropped, scaled and summed, so that tempo and pitch move together
+ * (sox `speed`).  sep_mix_draw and sep_mix_render are unchanged; the two entry points below are their twins.
+ * SPEEDS.  A list of J distinct integer percentages P_j, 1 <= J <= SEP_MIX_MAX_SPEEDS, SEP_MIX_SPEED_MIN <= P_j <= SEP_MIX_SPEED_MAX.  For a speed P:
+ * g = gcd(P, 100), o = P / g, u = 100 / g, and the filter is the resampler's (above: orig_freq = P, new_freq = 100, lowpass_filter_width 6, rolloff
+ * 0.99, sinc_interp_hann) in its compact form: fp32 table[k][p] (Kc rows of u, tap-major), first[p], Kc, width.  Over the whole range width <= 13,
+ * Kc <= 25 <= SEP_MIX_SPEED_MAX_TAPS and Kc u <= 2500 (25 taps of 100 phases at P = 199; Kc u <= 1300 for P < 100).  P = 100 is the identity:
+ * o = u = 1, no filter, exactly the copy formula of sep_mix_render.
+ * CONVENTION.  The perturbed utterance is the utterance resampled from rate P to rate 100: len' = ceil(u len / o) samples, a tone of frequency f comes
+ * out at f P / 100 -- P > 100 is shorter and higher.  (A 1 kHz tone at 8 kHz: 949.2 Hz at P = 95, 1050.8 Hz at P = 105, RMS ratios 0.99998 and 1.0005.)
+ * The level is NOT renormalised after the perturbation: gain = level[u] * gain_table[g] as in sep_mix_draw.
+ * A PERTURBED SAMPLE.  x is the raw sample (the int16 integer, or the fp32 value), zero outside [0, len) of its OWN utterance, never a neighbour's
+ * sample.  With m = i u + p:
+ *     acc  = sum over k < Kc, ascending, from +0.0, in fp64, of (double)table[k][p] * (double)x[i o + first[p] + k - width]
+ *     v[m] = (float)acc
+ * Every product is exact in fp64 (24 x 16 or 24 x 24 bits), so a fused and an unfused multiply-add give the same bits: device, numpy and the host
+ * simulation agree bit for bit.
+ * A ROW.  src[b][i][t] = gain * (v[start + t - lead] * scale) where lead <= t and t - lead < len' - start, +0.0f elsewhere; scale as in sep_mix_render.
+ * The mixture is summed in ascending order, the noise row added last.
+ * THE DRAW.  Speaker, utterance and gain index as in sep_mix_draw.  The speed index of source i is j = below(word(.., 4 n + 3 + i), J) -- draws
+ * 0 .. 4 n + 2 are taken, so nothing existing moves -- and the position is drawn from len' in place of len (formed in int64, clamped into [1, 2^31)),
+ * with draw 2 n + i as before.  The noise row is never perturbed.  Known answers:
+ *     word(1234, 0, 11) = 0x718ad7f33aef0177 (below 3: 1)   word(1234, 0, 12) = 0x0de521a7eba82090 (0)   word(1234, 1, 11) = 0x5f314ef19e801a70 (1)
+ *     word(0, 0, 7) = 0x915f11bbbfb2963d (1)                word(2^63, 2^40 + 3, 42) = 0xd90fbd8340eb6aa8 (2)
+ * DESCRIPTORS.  desc is int32 (J, SEP_MIX_SPEED_DESC) in device memory: {o, u, width, Kc, offset of table[0][0] in filter_table (floats), offset of
+ * first[0] in filter_first (entries), P, 0}; an identity speed is {1, 1, 0, 1, 0, 0, 100, 0}.  filter_table (table_numel floats) and filter_first
+ * (first_numel int32) hold the speeds' tables and `first` one behind the other.
+ *   sep_mix_draw_speed    sep_mix_draw plus desc, J and the output speed int32 (B, R): j per source, -1 for the noise row.  The plan stays (B, R, 4), the
+ *                         counter protocol is sep_mix_draw's.  With one identity speed the plan and the gains are sep_mix_draw's.
+ *   sep_mix_render_speed  sep_mix_render plus speed, desc, J and the filter buffers with their sizes.  One workgroup owns a tile of 2048 (int16) or 1024
+ *                         (fp32) output samples of one item and loops over its rows; for a perturbed row it stages the row's filter and the input span of
+ *                         the tile in LDS (aligned 16-byte loads, a word only where it holds a sample of the utterance), sums the taps in fp64, and
+ *                         accumulates the mixture in registers across rows.  Copy rows (j = -1, o == u) take sep_mix_render's formula in the same kernel.
+ *                         Every element is written once, no atomics, two runs give the same bits.  Instances: "mix_render_speed<int16>" and
+ *                         "mix_render_speed<float>" (T % 4 == 0, outputs 16-byte aligned: 16-byte stores), "mix_render_speed_scalar<int16>" and
+ *                         "mix_render_speed_scalar<float>" otherwise.
+ * The plan, speed and desc are device memory the library cannot look at.  Whatever they hold: the utterance is clamped into [0, U), j into [-1, J)
+ * (below -1 reads as -1), start into [0, len' - 1], o into [1, SEP_MIX_SPEED_MAX], u into [1, 100], width into [0, SEP_MIX_SPEED_MAX_TAPS], Kc into
+ * [1, SEP_MIX_SPEED_MAX_TAPS], every index into filter_table and filter_first into [0, table_numel) and [0, first_numel), every first[p] and every LDS index
+ * into the allocation; corpus reads stay inside the utterance and writes inside the outputs.
+ * Refused with a message before any launch: what the plain calls refuse, a null pointer, J outside [1, SEP_MIX_MAX_SPEEDS], table_numel outside
+ * [1, SEP_MIX_MAX_SPEEDS * SEP_MIX_SPEED_MAX_TAPS * 100], first_numel outside [1, SEP_MIX_MAX_SPEEDS * 100], samples not aligned to their own size.
+ * Not offered: perturbing the noise row, non-integer percentages, renormalising the level after the perturbation. */
+#define SEP_MIX_MAX_SPEEDS 16
+#define SEP_MIX_SPEED_MIN 50
+#define SEP_MIX_SPEED_MAX 200
+#define SEP_MIX_SPEED_MAX_TAPS 32
+#define SEP_MIX_SPEED_DESC 8
+int sep_mix_draw_speed(const int64_t* offsets, const int32_t* spk_first, int U, int S, const int64_t* noise_offsets, int U_noise, const float* level,
+                       const float* gain_table, int G, const float* noise_level, const float* noise_gain_table, int G_noise, int64_t* counter, int64_t seed,
+                       int64_t item_stride, int64_t item_first, int B, int n, int T, const int32_t* desc, int J, int64_t* plan, float* gain, int32_t* speed,
+                       sep_stream_t stream);
+int sep_mix_render_speed(const void* samples, int kind, const int64_t* offsets, int U, const void* noise_samples, const int64_t* noise_offsets, int U_noise,
+                         const int64_t* plan, const float* gain, const int32_t* speed, const int32_t* desc, int J, const float* filter_table, int64_t table_numel,
+                         const int32_t* filter_first, int64_t first_numel, int B, int n, int T, float* sources, float* mixture, float* noise, sep_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

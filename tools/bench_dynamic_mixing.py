@@ -13,6 +13,14 @@ Medians (and p99) of the HIP-event times; the kernels move about 8 MB per paper-
 is reported.
 
     python tools/bench_dynamic_mixing.py [--reps 50] [--warmup 5] [--steps 50] [--workers 16] [--out profiles/r20_dynamic_mixing.json]
+
+With --speeds 95,100,105 the tool measures speed perturbation instead (sep_mix_draw_speed, sep_mix_render_speed) and writes
+profiles/r21_dynamic_mixing_speed.json:
+    1. mixer      one mixer() call at the two shapes with speeds and without, the two alternating in one loop
+    2. composed   the same perturbation from what the library had before: per drawn row resample() of the whole utterance on the device, then crop,
+                  gain and sum in torch, on the speed mixer's own plans (the outputs agree with the kernel's to the resampler's rounding)
+    3. step       the recorded paper-best step fed by either mixer
+Bytes are counted for the render only (int16 span reads and fp32 writes); no fraction of a roof is reported.
 """
 import argparse
 import json
@@ -98,14 +106,130 @@ def write_wav_folder(torch, root, mixtures=320, seed=1):
     return lst
 
 
+def _timed(torch, fn, reps):
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return ms
+
+
+def composed_from_resample(torch, mixer):
+    """the batch of the speed mixer's last plan formed with resample() per row: whole-utterance resampling, then crop, gain and sum in torch"""
+    from sepkernels.resample import resample
+    c, T = mixer.corpus, mixer.samples
+    plan, gain, speed = mixer.plan[0].tolist(), mixer.plan[1], mixer.speed.tolist()
+    rows = []
+    for b, item in enumerate(plan):
+        for i, (u, start, lead, _) in enumerate(item):
+            x = c.utterance(u).to(torch.float32)
+            P = mixer.speeds[speed[b][i]]
+            v = x if P == 100 else resample(x, P, 100)
+            row = torch.zeros(T, device=x.device)
+            count = min(T - lead, v.numel() - start)
+            row[lead:lead + count] = gain[b, i] * (v[start:start + count] * 2.0 ** -15)
+            rows.append(row)
+    sources = torch.stack(rows).view(len(plan), len(plan[0]), T)
+    return sources.sum(1, keepdim=True), sources
+
+
+def speed_main(args, speeds):
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_dynamic_mixing.py measures on the GPU: none is visible")
+    import sepkernels
+    from bench_legs import PAPER
+    from criterion.pit import PIT1d
+    from criterion.sdr import NegSISDR
+    from models.conv_tasnet import ConvTasNet
+    from sepkernels.mixing import DynamicMixer
+    from sepkernels.train import FusedTrainStep
+    dev = torch.device("cuda", 0)
+    rows = []
+    corpus = synthetic_corpus(torch, dev)
+    for B, n, t in SHAPES:
+        plain = DynamicMixer(corpus, n_sources=n, samples=t, batch_size=B, seed=111)
+        fast = DynamicMixer(corpus, n_sources=n, samples=t, batch_size=B, seed=111, speeds=speeds)
+        for _ in range(args.warmup):
+            plain(), fast()
+        torch.cuda.synchronize()
+        ms = {"plain": [], "speed": []}
+        for _ in range(args.reps):                      # the two alternate: one box, one minute
+            ms["plain"] += _timed(torch, plain, 1)
+            ms["speed"] += _timed(torch, fast, 1)
+            kernel = sepkernels.last_kernel()
+        perturbed = sum(1 for P in speeds if P != 100) / len(speeds)
+        for name in ("plain", "speed"):
+            med, p99 = _stats(ms[name])
+            rows.append(dict(case="mixer", speeds=list(speeds) if name == "speed" else None, shape=[B, n, t], instance=kernel if name == "speed" else "mix_render_vec<int16,8>",
+                             ms_median=med, ms_p99=p99, ms_mean=round(sum(ms[name]) / len(ms[name]), 4), bytes_written=4 * B * (n + 1) * t, bytes_read_about=2 * B * n * t,
+                             fp64_multiply_adds_about=int(13 * B * n * t * perturbed) if name == "speed" else 0,
+                             seconds_of_audio_per_second=round(B * t / SR / (med * 1e-3), 1)))
+            print(json.dumps(rows[-1]), flush=True)
+        # 2. the same perturbation composed from resample(): on the speed mixer's plans, compared with its output first
+        mixture, sources = fast()
+        ref_mix, ref_src = composed_from_resample(torch, fast)
+        err = float((sources - ref_src).abs().max())
+        for _ in range(2):
+            fast.draw()
+            composed_from_resample(torch, fast)
+        torch.cuda.synchronize()
+        reps = max(5, args.reps // 5)
+
+        def both():
+            fast.draw()
+            composed_from_resample(torch, fast)
+        ms_c = _timed(torch, both, reps)
+        med, p99 = _stats(ms_c)
+        rows.append(dict(case="composed from resample()", speeds=list(speeds), shape=[B, n, t], reps=reps, ms_median=med, ms_p99=p99, ms_mean=round(sum(ms_c) / len(ms_c), 4),
+                         launches_about="one resample per perturbed row, then crop, gain, stack and sum in torch", max_abs_difference_from_the_kernel=err))
+        print(json.dumps(rows[-1]), flush=True)
+
+    # 3. the recorded paper-best step fed by either mixer, alternating blocks
+    B = 16
+    for name, sp in (("plain", None), ("speed", speeds), ("plain", None), ("speed", speeds)):
+        torch.manual_seed(111)
+        model = ConvTasNet(**PAPER).to(dev)
+        step = FusedTrainStep(model, PIT1d(NegSISDR(), n_sources=2), lr=1e-3, max_norm=5.0, auto_record=True)
+        mixer = DynamicMixer(corpus, n_sources=2, samples=T, batch_size=B, seed=111, speeds=sp)
+
+        def steps():
+            for _ in range(args.steps + args.warmup + 2):
+                mixture, sources = mixer()
+                yield step(mixture, sources)
+        ms_s = _intervals(torch, steps(), args.steps, args.warmup)
+        med, p99 = _stats(ms_s)
+        rows.append(dict(case="step", fed_by=name + " mixer", speeds=None if sp is None else list(sp), shape=[B, 2, T], recorded=step._seq is not None, steps_timed=len(ms_s),
+                         ms_per_step_median=med, ms_per_step_p99=p99, ms_per_step_mean=round(sum(ms_s) / len(ms_s), 4)))
+        print(json.dumps(rows[-1]), flush=True)
+        del model, step
+    doc = dict(tool="tools/bench_dynamic_mixing.py --speeds " + ",".join(str(P) for P in speeds), device=torch.cuda.get_device_name(0), reps=args.reps, warmup=args.warmup,
+               steps=args.steps, timing="HIP events, median and p99; plain and speed mixer alternate in one loop",
+               corpus=dict(utterances=corpus.num_utterances, speakers=corpus.num_speakers, kind="int16"), rows=rows)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--workers", type=int, default=16)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r20_dynamic_mixing.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--speeds", default=None, help="integer percentages such as 95,100,105: measure speed perturbation (profiles/r21_dynamic_mixing_speed.json)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "r21_dynamic_mixing_speed.json" if args.speeds else "r20_dynamic_mixing.json")
+    if args.speeds:
+        return speed_main(args, tuple(int(P) for P in args.speeds.split(",")))
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_dynamic_mixing.py measures on the GPU: none is visible")

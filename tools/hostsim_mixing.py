@@ -6,7 +6,11 @@ index out of range either way, start >= len, lead negative or >= T, NaN gains), 
 program is built with -fsanitize=address,undefined (the runtime is linked in; nothing is preloaded and no Python is involved in the run): a read
 outside the corpus's storage, a write outside an output, undefined arithmetic on a hostile plan.
 
-    python tools/hostsim_mixing.py [--asan]
+    python tools/hostsim_mixing.py [--asan] [--speed]
+
+--speed builds and runs tools/hostsim/mixing_speed_main.cpp instead: the same for sep_mix_draw_speed and sep_mix_render_speed -- the speed cases against the
+definition in plain loops, and hostile speed indices (out of range either way), start >= len', leads, a one-sample utterance and descriptor fields out
+of bounds on exactly-sized filter buffers.
 
 build_library(workdir) gives tests/test_dynamic_mixing_cpu.py a host-simulation library of csrc/mixing.hip and csrc/runtime.hip alone (the
 recorded-sequence case there needs csrc/sequence.hip and with it every file: tools/hostsim.py::build)."""
@@ -49,7 +53,8 @@ def main():
     flags = ["-std=c++17", "-O1", "-pthread"] + (["-g", "-fsanitize=" + kind, "-fno-omit-frame-pointer"] if kind else [])
     with tempfile.TemporaryDirectory() as d:
         exe = os.path.join(d, "mixing_host")
-        subprocess.check_call([cxx] + flags + _includes(d) + _sources(d) + [os.path.join(HOSTSIM_DIR, "mixing_main.cpp"), "-o", exe])
+        driver = "mixing_speed_main.cpp" if "--speed" in sys.argv else "mixing_main.cpp"
+        subprocess.check_call([cxx] + flags + _includes(d) + _sources(d) + [os.path.join(HOSTSIM_DIR, driver), "-o", exe])
         env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
         r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=900)
     markers = ("ERROR: AddressSanitizer", "runtime error:") if kind else ()
