@@ -345,7 +345,11 @@ extern "C" int sep_attn_fwd(const float* qkv, float* o, float* lse, int N, int L
     SEP_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "sep_attn_fwd: dropout rate %g", (double)p_drop);
     const att_args a = att_make(qkv, nullptr, nullptr, nullptr, nullptr, o, lse, L, H, scale, p_drop, seed);
     /* waves per workgroup = 32-query blocks that share one K / V fill: all of a sequence up to 256 steps */
-#define SEP_ATF_ONE(DD, MLL, NWW) hipLaunchKernelGGL((attn_fwd_kernel<DD, MLL, NWW>), dim3((L + 32 * NWW - 1) / (32 * NWW), H, N), dim3(64 * NWW), 0, (hipStream_t)stream, a)
+#define SEP_ATF_ONE(DD, MLL, NWW)                                                                                                                             \
+    do {                                                                                                                                                      \
+        sep_set_kernel("attn_fwd<" #DD "," #MLL "," #NWW ">");                                                                                                \
+        hipLaunchKernelGGL((attn_fwd_kernel<DD, MLL, NWW>), dim3((L + 32 * NWW - 1) / (32 * NWW), H, N), dim3(64 * NWW), 0, (hipStream_t)stream, a);          \
+    } while (0)
 #define SEP_ATF(DD)                                  \
     do {                                             \
         if (L <= 64) SEP_ATF_ONE(DD, 64, 2);         \
@@ -370,6 +374,7 @@ extern "C" int sep_attn_bwd(const float* qkv, const float* o, const float* dout,
 #define SEP_ATB_ONE(DD, MLL, NWW)                                                                                                                             \
     do {                                                                                                                                                      \
         const dim3 grid((L + 32 * NWW - 1) / (32 * NWW), H, N);                                                                                               \
+        sep_set_kernel("attn_bwd<" #DD "," #MLL "," #NWW ">");                                                                                                \
         hipLaunchKernelGGL((attn_bwd_q_kernel<DD, MLL, NWW>), grid, dim3(64 * NWW), 0, (hipStream_t)stream, a);                                               \
         hipLaunchKernelGGL((attn_bwd_kv_kernel<DD, MLL, NWW>), grid, dim3(64 * NWW), 0, (hipStream_t)stream, a);                                              \
     } while (0)

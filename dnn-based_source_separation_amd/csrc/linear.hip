@@ -261,11 +261,13 @@ __global__ __launch_bounds__(256) void chunk_tokens_kernel(const float* __restri
 
 template <int MODE>
 int lin_launch(const lin_args& p, int ti, int tj, unsigned grid, hipStream_t stream) {
-#define SEP_LIN(TI, TJ) hipLaunchKernelGGL((linear_kernel<MODE, TI, TJ>), dim3(grid), dim3(256), 0, stream, p)
-    if (ti == 128 && tj == 128) SEP_LIN(128, 128);
-    else if (ti == 128 && tj == 64) SEP_LIN(128, 64);
-    else if (ti == 64 && tj == 128) SEP_LIN(64, 128);
-    else SEP_LIN(64, 64);
+#define SEP_LIN(TI, TJ)                                                                                                                          \
+    sep_set_kernel(MODE == LIN_FWD ? "linear<fwd," #TI "," #TJ ">" : MODE == LIN_BWD_INPUT ? "linear<bwd_input," #TI "," #TJ ">" : "linear<bwd_weight," #TI "," #TJ ">"); \
+    hipLaunchKernelGGL((linear_kernel<MODE, TI, TJ>), dim3(grid), dim3(256), 0, stream, p)
+    if (ti == 128 && tj == 128) { SEP_LIN(128, 128); }
+    else if (ti == 128 && tj == 64) { SEP_LIN(128, 64); }
+    else if (ti == 64 && tj == 128) { SEP_LIN(64, 128); }
+    else { SEP_LIN(64, 64); }
 #undef SEP_LIN
     return 0;
 }
@@ -318,6 +320,7 @@ static int chunk_tokens(const float* src, float* dst, int B, int F, int S, int K
     const long gz = (long)B * ((F + 31) / 32);
     SEP_REQUIRE(S <= 65535 && gz <= 65535, "%s: S = %d chunks and B x ceil(F / 32) = %ld must fit a grid dimension (65535)", name, S, gz);
     const dim3 grid((K + 31) / 32, S, (unsigned)gz);
+    sep_set_kernel(to_tokens ? "chunk_tokens<true>" : "chunk_tokens<false>");
     if (to_tokens) hipLaunchKernelGGL((chunk_tokens_kernel<true>), grid, dim3(256), 0, stream, src, dst, F, S, K, inter);
     else hipLaunchKernelGGL((chunk_tokens_kernel<false>), grid, dim3(256), 0, stream, src, dst, F, S, K, inter);
     return 0;

@@ -410,18 +410,22 @@ bool few_sequences(int nseq, int reverse, int force) {
 template <int H>
 int launch_fwd(const float* xg, const float* whh, float* hout, float* gates, float* cstate, int nseq, int L, int reverse, int force, int hs, hipStream_t st) {
     if (few_sequences(nseq, reverse, force)) {
+        sep_set_kernel(H == 16 ? "lstm_fwd4<16>" : H == 32 ? "lstm_fwd4<32>" : H == 64 ? "lstm_fwd4<64>" : "lstm_fwd4<128>");
         hipLaunchKernelGGL((lstm_fwd4_kernel<H>), dim3((nseq + NS4 - 1) / NS4, reverse == 2 ? 2 : 1), dim3(H * 4), 0, st, xg, whh, hout, gates, cstate, nseq, L, reverse, hs);
         return 0;
     }
+    sep_set_kernel(H == 16 ? "lstm_fwd<16>" : H == 32 ? "lstm_fwd<32>" : H == 64 ? "lstm_fwd<64>" : "lstm_fwd<128>");
     hipLaunchKernelGGL((lstm_fwd_kernel<H>), dim3((nseq + LSTM_NS - 1) / LSTM_NS, reverse == 2 ? 2 : 1), dim3(H * 4), 0, st, xg, whh, hout, gates, cstate, nseq, L, reverse, hs);
     return 0;
 }
 template <int H>
 int launch_bwd(const float* dhout, const float* gates, const float* cstate, const float* whh, float* dxg, int nseq, int L, int reverse, int force, int hs, hipStream_t st) {
     if (few_sequences(nseq, reverse, force)) {
+        sep_set_kernel(H == 16 ? "lstm_bwd4<16>" : H == 32 ? "lstm_bwd4<32>" : H == 64 ? "lstm_bwd4<64>" : "lstm_bwd4<128>");
         hipLaunchKernelGGL((lstm_bwd4_kernel<H>), dim3((nseq + NS4 - 1) / NS4, reverse == 2 ? 2 : 1), dim3(H * 4), 0, st, dhout, gates, cstate, whh, dxg, nseq, L, reverse, hs);
         return 0;
     }
+    sep_set_kernel(H == 16 ? "lstm_bwd<16>" : H == 32 ? "lstm_bwd<32>" : H == 64 ? "lstm_bwd<64>" : "lstm_bwd<128>");
     hipLaunchKernelGGL((lstm_bwd_kernel<H>), dim3((nseq + LSTM_NS - 1) / LSTM_NS, reverse == 2 ? 2 : 1), dim3(H * 4), 0, st, dhout, gates, cstate, whh, dxg, nseq, L, reverse, hs);
     return 0;
 }

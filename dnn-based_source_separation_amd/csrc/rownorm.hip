@@ -209,8 +209,8 @@ extern "C" int sep_rownorm_fwd(const float* x, const float* res, const float* ga
     SEP_REQUIRE(p_drop >= 0.f && p_drop < 1.f && (p_drop == 0.f || res), "sep_rownorm_fwd: 0 <= p_drop < 1, and only on a residual branch");
     const rn_drop d = rn_make_drop(p_drop, seed);
     const int grid = sep_rownorm_parts(rows, C), nj = (C + 255) / 256;
-#define SEP_RNF(NJ) hipLaunchKernelGGL((rownorm_fwd_kernel<NJ>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, res, gamma, beta, s, y, stat, rows, C, eps, d)
-    if (nj == 1) SEP_RNF(1); else if (nj == 2) SEP_RNF(2); else if (nj == 3) SEP_RNF(3); else SEP_RNF(4);
+#define SEP_RNF(NJ) sep_set_kernel("rownorm_fwd<" #NJ ">"); hipLaunchKernelGGL((rownorm_fwd_kernel<NJ>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, res, gamma, beta, s, y, stat, rows, C, eps, d)
+    if (nj == 1) { SEP_RNF(1); } else if (nj == 2) { SEP_RNF(2); } else if (nj == 3) { SEP_RNF(3); } else { SEP_RNF(4); }
 #undef SEP_RNF
     SEP_CHECK_LAUNCH("sep_rownorm_fwd");
     return 0;
@@ -222,8 +222,8 @@ extern "C" int sep_rownorm_bwd(const float* dy, const float* s, const float* gam
     SEP_REQUIRE(p_drop >= 0.f && p_drop < 1.f && (p_drop > 0.f) == (dres != nullptr), "sep_rownorm_bwd: dres exactly when the branch was dropped out");
     const rn_drop d = rn_make_drop(p_drop, seed);
     const int grid = sep_rownorm_parts(rows, C), nj = (C + 255) / 256;
-#define SEP_RNB(NJ) hipLaunchKernelGGL((rownorm_bwd_kernel<NJ>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, s, gamma, stat, ds, dres, part, rows, C, d)
-    if (nj == 1) SEP_RNB(1); else if (nj == 2) SEP_RNB(2); else if (nj == 3) SEP_RNB(3); else SEP_RNB(4);
+#define SEP_RNB(NJ) sep_set_kernel("rownorm_bwd<" #NJ ">"); hipLaunchKernelGGL((rownorm_bwd_kernel<NJ>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, s, gamma, stat, ds, dres, part, rows, C, d)
+    if (nj == 1) { SEP_RNB(1); } else if (nj == 2) { SEP_RNB(2); } else if (nj == 3) { SEP_RNB(3); } else { SEP_RNB(4); }
 #undef SEP_RNB
     SEP_CHECK_LAUNCH("sep_rownorm_bwd");
     return 0;
@@ -231,6 +231,7 @@ extern "C" int sep_rownorm_bwd(const float* dy, const float* s, const float* gam
 
 extern "C" int sep_relu_drop_fwd(const float* h, float* a, long n, float p_drop, unsigned long long seed, sep_stream_t stream) {
     SEP_REQUIRE(h && a && n > 0 && n % 4 == 0 && p_drop >= 0.f && p_drop < 1.f, "sep_relu_drop_fwd: bad arguments (n a multiple of 4, 0 <= p_drop < 1)");
+    sep_set_kernel("relu_drop_fwd");
     hipLaunchKernelGGL(relu_drop_fwd_kernel, dim3(rn_flat_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, h, a, n / 4, rn_make_drop(p_drop, seed));
     SEP_CHECK_LAUNCH("sep_relu_drop_fwd");
     return 0;
@@ -238,6 +239,7 @@ extern "C" int sep_relu_drop_fwd(const float* h, float* a, long n, float p_drop,
 
 extern "C" int sep_relu_drop_bwd(const float* dy, const float* a, float* dh, long n, float p_drop, sep_stream_t stream) {
     SEP_REQUIRE(dy && a && dh && n > 0 && n % 4 == 0 && p_drop >= 0.f && p_drop < 1.f, "sep_relu_drop_bwd: bad arguments (n a multiple of 4, 0 <= p_drop < 1)");
+    sep_set_kernel("relu_drop_bwd");
     hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3(rn_flat_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, dy, a, dh, n / 4, rn_make_drop(p_drop, 0ull).keep_inv);
     SEP_CHECK_LAUNCH("sep_relu_drop_bwd");
     return 0;
