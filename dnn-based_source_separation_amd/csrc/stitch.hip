@@ -4,7 +4,7 @@
 // over minutes, chunk counts outside the trained range).  The recording is cut into W overlapping windows of the trained length `win` at stride
 // `hop` (sep_segment), every window is separated on its own, and the n outputs of a window come in an order of their own.  The three kernels here
 // undo that order and join the windows: sep_stitch_cost measures every (output of window w, output of window w + 1) pair on the O = win - hop
-// samples the two windows share, sep_assign (csrc/loss.hip) matches them, sep_stitch_chain composes the per-boundary matchings into one
+// samples the two windows share, sep_assign (csrc/assign.hip) matches them, sep_stitch_chain composes the per-boundary matchings into one
 // permutation per window relative to the first, sep_stitch_ola cross-fades the aligned windows into n tracks.  win / 2 <= hop < win: a sample
 // lies in at most two windows, so the output is a function of at most two inputs and is written once, without a normaliser.  The contract is in
 // include/sepkernels.h.  The reference has nothing of the kind.

@@ -14,7 +14,7 @@ stitch() is the part after the model.  For estimates (B, W, n, win) of W windows
                          c = est[b][w][perm_abs[b][w][s]][k], a = est[b][w - 1][perm_abs[b][w - 1][s]][hop + k], g = (k + 0.5) / O
 win / 2 <= hop < win: a sample lies in at most two windows and the cross-fade weights add to one.  On contiguous fp32 device tensors with
 n <= 64 this is four launches without a host synchronisation in between (sep_stitch_cost, sep_assign, sep_stitch_chain, sep_stitch_ola:
-csrc/stitch.hip, csrc/loss.hip); everything else -- CPU tensors beside the HIP library, fp64, n > 64, a strided view -- is the same
+csrc/stitch.hip, csrc/assign.hip); everything else -- CPU tensors beside the HIP library, fp64, n > 64, a strided view -- is the same
 definitions composed in torch, with criterion.hungarian._assign for the matching.  Inference only: nothing here carries a gradient.
 """
 import torch

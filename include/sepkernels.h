@@ -748,7 +748,7 @@ int sep_online_state_export(const int32_t* slots, int num_streams, const int64_t
 int sep_online_state_import(const int32_t* slots, int num_streams, int64_t* frames, float* carry, int carry_len, double* sums, int sums_len,
                             float* rings, int64_t rings_len, float* tail, int tail_len, const void* blob, int64_t row_pitch, sep_stream_t stream);
 
-/* ---- BSS-eval v3 ("sources"): SDR, SIR and SAR of the test recipes (ABI 23, additive; csrc/loss.hip) --------------------------------------------
+/* ---- BSS-eval v3 ("sources"): SDR, SIR and SAR of the test recipes (ABI 23, additive; csrc/bss.hip) --------------------------------------------
  * The metric of Vincent et al. 2006 as the reference's testers call it (src/utils/bss.py -> mir_eval.separation.bss_eval_sources,
  * egs/wsj0-mix/common/src/driver.py:291-309).  For references r_0 .. r_{n-1} and estimates e_0 .. e_{m-1} of T_b samples, all extended by flen - 1
  * zeros: P_i(e_j) is the least-squares projection of e_j on { r_i delayed by tau, tau = 0 .. flen - 1 }, P_all(e_j) the projection on the delayed
@@ -780,7 +780,7 @@ int sep_bss_xcorr(const float* a, const float* c, const int32_t* lengths, double
 int sep_bss_energies(const float* ref, const float* est, const double* filt_all, const double* filt_one, const int32_t* lengths, double* out,
                      double* scratch, size_t scratch_bytes, int B, int n, int m, int T, int flen, sep_stream_t stream);
 
-/* ---- BSS-eval v4 ("images"): museval's framewise SDR, ISR, SIR and SAR of music separation (ABI 23, additive; csrc/loss.hip) -------------------
+/* ---- BSS-eval v4 ("images"): museval's framewise SDR, ISR, SIR and SAR of music separation (ABI 23, additive; csrc/bss.hip) -------------------
  * The figure music separation is published with, as museval 0.4's metrics.bss_eval computes it for eval_mus_track (window = hop = 1 s,
  * filters_len = 512, framewise_filters = False, compute_permutation = False, images version; the reference's music tester ends there,
  * egs/musdb18/conv-tasnet/src/adhoc_driver.py:352-380).  Restated from that code; agreement with the museval PACKAGE itself is untested, it is on
@@ -817,7 +817,7 @@ int sep_bss_image_energies(const float* ref, const float* est, const double* fil
                            double* scratch, size_t scratch_bytes, int B, int n, int C, int T, int flen, int window, int hop, int nwin,
                            sep_stream_t stream);
 
-/* ---- Mixture invariant training (MixIT, Wisdom et al. 2020; ABI 23, additive; csrc/loss.hip, criterion/mixit.py) ---------------------------------
+/* ---- Mixture invariant training (MixIT, Wisdom et al. 2020; ABI 23, additive; csrc/mixit.hip, criterion/mixit.py) ---------------------------------
  * M estimates est (B, M, T) of the sum of N reference mixtures tgt (B, N, T), fp32 rows of pitch T.  An assignment hands every estimate to exactly
  * one mixture; its code is sum_m n(m) N^(M-1-m) (itertools.product(range(N), repeat=M) order, estimate 0 most significant).  The remix of
  * mixture n is y_n = sum of the estimates with n(m) = n (zero for an empty set), and the measure of (y_n, x_n) is a function of three inner
@@ -854,7 +854,7 @@ int sep_mixit_search(const double* gram, int B, int M, int N, int kind, int maxi
 int sep_mixit_bwd(const float* est, const float* tgt, const double* gram, const int64_t* best_idx, const float* gw, float* d_est, int B, int M,
                   int N, int T, int kind, double eps, double tau, sep_stream_t stream);
 
-/* ---- Optimal-permutation (Hungarian) training (Dovrat, Nachmani, Wolf 2021; ABI 23, additive; csrc/loss.hip, criterion/hungarian.py) --------------
+/* ---- Optimal-permutation (Hungarian) training (Dovrat, Nachmani, Wolf 2021; ABI 23, additive; csrc/assign.hip, criterion/hungarian.py) --------------
  * n estimates est (B, n, T) of n targets tgt (B, n, T), fp32 rows of pitch T.  The loss is the best of the n! ways to pair them, found as a linear
  * assignment problem on the n x n matrix of pair measures in O(n^3), not by a table of permutations.  1 <= n <= SEP_ASSIGN_MAX_N = 64 (a column
  * per lane of one wavefront), B <= 65535 for the calls that walk the waveforms, T >= 1.  Anything else is refused with a message before any launch.

@@ -39,7 +39,8 @@ def test_every_declared_symbol_is_exported_and_bound():
 def test_translation_units_are_listed_once_and_shared_helpers_defined_once():
     """the build and the host simulation compile the same set of files, which is csrc/*.hip; every entry point of the header is defined in
     exactly one of them; runtime.hip holds the five runtime functions and nothing else; the 16-byte load / store, the dropout hash and the
-    wave fold exist in common.hpp alone (a copy under another name would be found here)"""
+    wave fold exist in common.hpp alone (a copy under another name would be found here); the 25 entry points of the criterion files
+    (loss, optim, bss, mixit, assign) each have their file, and sdr_terms and the pair measure are defined in loss_common.hpp alone"""
     for p in (ROOT, os.path.join(ROOT, "tools")):
         if p not in sys.path:
             sys.path.insert(0, p)
@@ -49,7 +50,7 @@ def test_translation_units_are_listed_once_and_shared_helpers_defined_once():
     on_disk = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
     assert sorted(entry.HIP_SOURCES) == sorted(f + ".hip" for f in hostsim.FILES) == on_disk
     assert len(on_disk) == len(set(entry.HIP_SOURCES)) == len(entry.HIP_SOURCES) == len(hostsim.FILES) >= 23
-    texts = {f: open(os.path.join(csrc, f)).read() for f in on_disk + ["common.hpp"]}
+    texts = {f: open(os.path.join(csrc, f)).read() for f in on_disk + ["common.hpp", "loss_common.hpp"]}
     defined = {f: re.findall(r'^extern "C" [\w\s\*]*?\b(sep_[a-z0-9_]+)\s*\([^;{]*\)\s*\{', t, flags=re.M) for f, t in texts.items()}
     homes = {n: [f for f, names in defined.items() for m in names if m == n] for n in _declared()}
     assert all(len(h) == 1 for h in homes.values()), {n: h for n, h in homes.items() if len(h) != 1}
@@ -57,6 +58,18 @@ def test_translation_units_are_listed_once_and_shared_helpers_defined_once():
     for n, home in (("sep_pw_gemm", "gemm.hip"), ("sep_pw_wgrad", "wgrad.hip"), ("sep_pw_wgrad_batch", "wgrad.hip"),
                     ("sep_reduce_slabs", "reduce.hip"), ("sep_f64_to_f32", "reduce.hip")):
         assert homes[n] == [home], n
+    criteria = {"loss.hip": "sisdr_dots sisdr_from_dots sisdr_bwd pit_search sinkhorn_fwd sinkhorn_bwd rowdiff_sums rowdiff_bwd",
+                "optim.hip": "sqnorm adam_step adam_step_dev",
+                "bss.hip": "bss_scratch_bytes bss_xcorr bss_energies bss_image_scratch_bytes bss_image_energies",
+                "mixit.hip": "mixit_scratch_bytes mixit_gram mixit_search mixit_bwd",
+                "assign.hip": "pair_gram_scratch_bytes pair_gram assign pair_assign pair_bwd"}
+    assert sum(len(names.split()) for names in criteria.values()) == 25
+    for home, names in criteria.items():
+        for n in names.split():
+            assert homes["sep_" + n] == [home], n
+    for helper in (r"\bsdr_terms\(", r"\b\w+_measure\("):     # what these files share is defined in their header alone
+        definition = r"^(?:__device__ |static |inline |__forceinline__ )+[\w\s\*]*?" + helper + r"[^;{]*\{"
+        assert [f for f, t in texts.items() if re.search(definition, t, flags=re.M)] == ["loss_common.hpp"], helper
     assert re.findall(r"^(?:extern \"C\" )?[\w\s\*]*?\b(\w+)\s*\([^;{]*\)\s*\{", texts["runtime.hip"], flags=re.M) == [
         "sep_set_error", "sep_last_error", "sep_set_kernel", "sep_last_kernel", "sep_version"]
     once = {r"\{\s*return \*reinterpret_cast<const float4\*>\(\w+\);\s*\}": 1,          # a one-line float4 load helper

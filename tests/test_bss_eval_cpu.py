@@ -1,4 +1,4 @@
-"""CPU: BSS-eval v3 ("sources") -- utils/bss.py, csrc/loss.hip: sep_bss_xcorr / sep_bss_energies, the `bss_eval` switch of recipes.trainer.Tester.
+"""CPU: BSS-eval v3 ("sources") -- utils/bss.py, csrc/bss.hip: sep_bss_xcorr / sep_bss_energies, the `bss_eval` switch of recipes.trainer.Tester.
 
 (a) utils.bss under SEPK_BSS_EVAL=native on an emulator of the two calls (BssEmu below, written from their contract in include/sepkernels.h)
     against the oracle of tests/test_bss_eval_gpu.py -- explicit delayed-reference matrix, numpy.linalg.lstsq, energy ratios; not the normal

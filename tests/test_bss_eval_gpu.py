@@ -1,4 +1,4 @@
-"""GPU: BSS-eval v3 ("sources") -- SDR, SIR, SAR -- on the device (utils/bss.py; csrc/loss.hip: sep_bss_xcorr, sep_bss_energies).
+"""GPU: BSS-eval v3 ("sources") -- SDR, SIR, SAR -- on the device (utils/bss.py; csrc/bss.hip: sep_bss_xcorr, sep_bss_energies).
 
 (a) the two kernels, case by case, against fp64 numpy restatements of their contract in include/sepkernels.h at 1e-12 relative (the kernels
     are fp64, only the order of summation differs): the lagged correlations against sums over explicitly zero-padded signals, the energies

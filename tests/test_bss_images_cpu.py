@@ -1,4 +1,4 @@
-"""CPU: BSS-eval v4 ("images") -- utils/bss.py: bss_eval_images_batch / bss_eval_images / eval_track; csrc/loss.hip: sep_bss_image_energies;
+"""CPU: BSS-eval v4 ("images") -- utils/bss.py: bss_eval_images_batch / bss_eval_images / eval_track; csrc/bss.hip: sep_bss_image_energies;
 recipes/evaluate_musdb18.py.
 
 (a) the metric against the oracle of tests/test_bss_images_gpu.py (explicit delayed-reference matrix, numpy.linalg.lstsq, numpy.convolve per

@@ -1,4 +1,4 @@
-"""GPU: BSS-eval v4 ("images") -- museval's framewise SDR, ISR, SIR, SAR -- on the device (utils/bss.py; csrc/loss.hip: sep_bss_image_energies).
+"""GPU: BSS-eval v4 ("images") -- museval's framewise SDR, ISR, SIR, SAR -- on the device (utils/bss.py; csrc/bss.hip: sep_bss_image_energies).
 
 (a) the kernel's nine sums per (source, frame) against an fp64 numpy restatement of its contract in include/sepkernels.h with GIVEN filters
     (numpy.convolve per frame segment) at 1e-12 relative: the kernel is fp64, only the order of summation differs.  The case functions take

@@ -1,4 +1,4 @@
-"""CPU: optimal-permutation (Hungarian) training -- criterion/hungarian.py, csrc/loss.hip: sep_pair_gram / sep_assign / sep_pair_assign / sep_pair_bwd,
+"""CPU: optimal-permutation (Hungarian) training -- criterion/hungarian.py, csrc/assign.hip: sep_pair_gram / sep_assign / sep_pair_assign / sep_pair_bwd,
 `--criterion hungarian` of recipes.train_conv_tasnet.
 
 (a) the cases of tests/test_hungarian_gpu.py (its textbook fp64 oracle) on an emulator of the four calls (HungarianEmu below, written from their

@@ -1,4 +1,4 @@
-"""GPU: optimal-permutation (Hungarian) training (criterion/hungarian.py; csrc/loss.hip: sep_pair_gram, sep_assign, sep_pair_assign, sep_pair_bwd).
+"""GPU: optimal-permutation (Hungarian) training (criterion/hungarian.py; csrc/assign.hip: sep_pair_gram, sep_assign, sep_pair_assign, sep_pair_bwd).
 
 The reference's src/criterion/hungarian.py is a stub, there is nothing to compare with.  The oracle is written here from the textbook: a
 plain-Python fp64 shortest-augmenting-path solver (`solve`), itself held to brute force over itertools.permutations for every matrix the

@@ -1,4 +1,4 @@
-"""CPU: mixture invariant training -- criterion/mixit.py, csrc/loss.hip: sep_mixit_gram / sep_mixit_search / sep_mixit_bwd, recipes.wsj0mix.MixtureOfMixtures,
+"""CPU: mixture invariant training -- criterion/mixit.py, csrc/mixit.hip: sep_mixit_gram / sep_mixit_search / sep_mixit_bwd, recipes.wsj0mix.MixtureOfMixtures,
 `--criterion mixit` of recipes.train_conv_tasnet.
 
 (a) the criterion-level cases of tests/test_mixit_gpu.py (its brute-force fp64 oracle) on an emulator of the three calls (MixitEmu below, written

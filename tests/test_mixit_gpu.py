@@ -1,4 +1,4 @@
-"""GPU: mixture invariant training (criterion/mixit.py; csrc/loss.hip: sep_mixit_gram, sep_mixit_search, sep_mixit_bwd).
+"""GPU: mixture invariant training (criterion/mixit.py; csrc/mixit.hip: sep_mixit_gram, sep_mixit_search, sep_mixit_bwd).
 
 The oracle is a brute-force MixIT in fp64 torch, written from the paper (Wisdom et al. 2020) and from the formulas stated in criterion/sdr.py
 -- the reference's src/criterion/mixit.py is a stub, there is nothing to compare with: every assignment of itertools.product(range(N),

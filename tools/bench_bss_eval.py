@@ -1,4 +1,4 @@
-"""BSS-eval benchmark (utils/bss.py; csrc/loss.hip: sep_bss_xcorr, sep_bss_energies): SDR / SIR / SAR of n = 2 sources at the production
+"""BSS-eval benchmark (utils/bss.py; csrc/bss.hip: sep_bss_xcorr, sep_bss_energies): SDR / SIR / SAR of n = 2 sources at the production
 filter length 512, T = 32000 and 80000 samples (4 s and 10 s at 8 kHz), B = 1 and B = 16 utterances per call.  One JSON line per (T, B):
 
     native_ms_median / _p99      utils.bss.bss_eval_sources_batch on device tensors, HIP events around the whole call (checks, kernels, solves,

@@ -1,4 +1,4 @@
-"""BSS-eval v4 ("images") benchmark (utils/bss.py; csrc/loss.hip: sep_bss_xcorr, sep_bss_image_energies): museval's framewise SDR / ISR / SIR /
+"""BSS-eval v4 ("images") benchmark (utils/bss.py; csrc/bss.hip: sep_bss_xcorr, sep_bss_image_energies): museval's framewise SDR / ISR / SIR /
 SAR of one MUSDB18-like track -- n = 4 stereo sources, filter length 512, window = hop = 44100 -- at T = 30 s and 240 s.  One JSON line per T:
 
     native_ms_median             utils.bss.bss_eval_images_batch on device tensors, HIP events around the whole call (checks, the two correlation

@@ -1,4 +1,4 @@
-"""Optimal-permutation training benchmark (criterion/hungarian.py; csrc/loss.hip: sep_pair_gram, sep_assign, sep_pair_assign, sep_pair_bwd) on one
+"""Optimal-permutation training benchmark (criterion/hungarian.py; csrc/assign.hip: sep_pair_gram, sep_assign, sep_pair_assign, sep_pair_bwd) on one
 MI355X.  Forward + backward of a permutation-invariant negative SI-SDR on (B, n, T) = (4, n, 32000) (4 s at 8 kHz), n in {2, 5, 10, 20}, three ways
 in the same session -- one JSON row per n:
 

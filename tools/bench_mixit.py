@@ -1,4 +1,4 @@
-"""MixIT benchmark (criterion/mixit.py; csrc/loss.hip: sep_mixit_gram, sep_mixit_search, sep_mixit_bwd): forward + backward of
+"""MixIT benchmark (criterion/mixit.py; csrc/mixit.hip: sep_mixit_gram, sep_mixit_search, sep_mixit_bwd): forward + backward of
 MixIT(NegThresholdedSNR()) on (B, M, T) estimates of (B, N, T) mixtures, T = 32000 (4 s at 8 kHz), on the kernel route and on the composed
 route (remixes for a block of assignments at a time, the criterion itself on them; forced by a subclass of the criterion, which the route
 selection does not take for the exact class) in the same session.  One JSON line per shape:

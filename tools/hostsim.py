@@ -79,6 +79,55 @@ def compiler():
     return None
 
 
+HOSTSIM_DIR = os.path.join(ROOT, "tools", "hostsim")
+
+
+def _units(d, files):
+    """the host copies of `files` written into `d`, plus the simulation's runtime; and the include flags they compile with"""
+    out = []
+    for f in files:
+        out.append(os.path.join(d, f + ".cpp"))
+        open(out[-1], "w").write(host_copy(f + ".hip"))
+    inc = ["-I", d, "-I", os.path.join(HOSTSIM_DIR, "include"), "-I", CSRC, "-I", os.path.join(ROOT, "include")]
+    return inc + out + [os.path.join(HOSTSIM_DIR, "sim_main.cpp")]
+
+
+def build_units(workdir, files, tag):
+    """-> path of a shared library with the entry points of the translation units `files` alone (a few seconds instead of the minute
+    the whole of csrc/ takes), for HostSimBackend: the per-feature tools' build_library"""
+    cxx = compiler()
+    if cxx is None:
+        raise RuntimeError("hostsim needs clang++")
+    so = os.path.join(workdir, "libsepkernels_hostsim_{}.so".format(tag))
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-fPIC", "-pthread", "-shared"] + _units(workdir, files) + ["-o", so])
+    return so
+
+
+def run_program(files, driver_cpp, exe_name, sanitize, timeout=900):
+    """the per-feature tools' main(): the host copies of `files` linked with tools/hostsim/<driver_cpp> into ONE PROGRAM and run.  sanitize:
+    the program is built with -fsanitize=address,undefined (the runtime is linked in; nothing is preloaded and no Python is involved in
+    the run) and the reports in its stderr are counted.  -> the process's exit status: 0 only for a clean run without reports"""
+    import tempfile
+    kind = "address,undefined" if sanitize else None
+    cxx = compiler()
+    if cxx is None:
+        print("needs clang++")
+        return 1
+    flags = ["-std=c++17", "-O1", "-pthread"] + (["-g", "-fsanitize=" + kind, "-fno-omit-frame-pointer"] if kind else [])
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, exe_name)
+        subprocess.check_call([cxx] + flags + _units(d, files) + [os.path.join(HOSTSIM_DIR, driver_cpp), "-o", exe])
+        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+        r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=timeout)
+    markers = ("ERROR: AddressSanitizer", "runtime error:") if kind else ()
+    reports = sum(r.stderr.count(mk) for mk in markers)
+    print(r.stdout[-3000:])
+    if reports or r.returncode:
+        print(r.stderr[-6000:])
+    print("{}: exit status {}, sanitizer reports: {}".format(kind or "plain", r.returncode, reports))
+    return 1 if reports or r.returncode else 0
+
+
 def build(workdir, sanitize=None):
     """-> path of libsepkernels_hostsim.so, built in `workdir`; sanitize: None, "address" or "thread" (the process that loads a
     sanitized build must run with that sanitizer's runtime preloaded, see `python tools/hostsim.py --asan | --tsan`)"""

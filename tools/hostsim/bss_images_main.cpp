@@ -1,4 +1,4 @@
-// Stand-alone driver for the host simulation of the BSS-eval v4 ("images") kernel (csrc/loss.hip: sep_bss_image_scratch_bytes,
+// Stand-alone driver for the host simulation of the BSS-eval v4 ("images") kernel (csrc/bss.hip: sep_bss_image_scratch_bytes,
 // sep_bss_image_energies): the shapes of tests/test_bss_images_gpu.py on buffers allocated to their exact sizes, two rows of different
 // lengths, checked against the contract of include/sepkernels.h restated here with plain double loops, at 1e-12 relative.  Samples beyond a
 // row's length hold NaN: reading one shows in the result.  Built and run by tools/hostsim_bss_images.py, plain or with

@@ -1,4 +1,4 @@
-// Stand-alone driver for the host simulation of the BSS-eval kernels (csrc/loss.hip: sep_bss_scratch_bytes, sep_bss_xcorr, sep_bss_energies):
+// Stand-alone driver for the host simulation of the BSS-eval kernels (csrc/bss.hip: sep_bss_scratch_bytes, sep_bss_xcorr, sep_bss_energies):
 // the kernel cases of tests/test_bss_eval_gpu.py on buffers allocated to their exact sizes, checked against the contract of
 // include/sepkernels.h restated here with plain double loops, at 1e-12 relative.  Samples beyond a row's length hold NaN: reading one shows in
 // the result.  Built and run by tools/hostsim_bss.py, plain or with -fsanitize=address,undefined (a program of its own: the

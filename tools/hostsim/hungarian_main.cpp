@@ -1,4 +1,4 @@
-// Stand-alone driver for the host simulation of the optimal-permutation kernels (csrc/loss.hip: sep_pair_gram_scratch_bytes, sep_pair_gram,
+// Stand-alone driver for the host simulation of the optimal-permutation kernels (csrc/assign.hip: sep_pair_gram_scratch_bytes, sep_pair_gram,
 // sep_assign, sep_pair_assign, sep_pair_bwd): n in {1, 9, 64} at T = 1 and T = 2 SEP_PAIR_SLAB + 17, every buffer allocated to its exact size and
 // pre-filled with NaN, checked against the contract of include/sepkernels.h restated here with plain double loops over the waveforms and a plain
 // O(n^3) shortest-augmenting-path solver; matrices with NaN and +-Inf must come back with a valid permutation.  Built and run by

@@ -1,5 +1,5 @@
 // Development / test tool (tools/hostsim.py): the pieces of the HIP programming model that the asm-free kernel files of csrc/ use
-// (filterbank.hip, tcn.hip, gln.hip, depthwise.hip, cln.hip, loss.hip, lstm.hip), restated for the HOST, so that the kernels' own source -- compiled as plain C++ with this
+// (filterbank.hip, tcn.hip, gln.hip, depthwise.hip, cln.hip, loss.hip, optim.hip, bss.hip, mixit.hip, assign.hip, lstm.hip), restated for the HOST, so that the kernels' own source -- compiled as plain C++ with this
 // directory in front of the include path -- runs as ordinary threads: one thread per lane of a workgroup, a pthread barrier per workgroup
 // and per wave, wave shuffles and the MFMA instructions as collective operations of a wave.  Not a general HIP emulator.  Known limits:
 // collectives must be reached by every lane of the wave / workgroup (true of these kernels; divergent shuffles would deadlock here),

@@ -1,4 +1,4 @@
-// Stand-alone driver for the host simulation of the MixIT kernels (csrc/loss.hip: sep_mixit_scratch_bytes, sep_mixit_gram, sep_mixit_search,
+// Stand-alone driver for the host simulation of the MixIT kernels (csrc/mixit.hip: sep_mixit_scratch_bytes, sep_mixit_gram, sep_mixit_search,
 // sep_mixit_bwd): R = M + N in {2, 10, 24} at T = 1 and T = 2 SEP_MIXIT_SLAB + 17, every buffer allocated to its exact size and pre-filled with
 // NaN, checked against the contract of include/sepkernels.h restated here with plain double loops over the waveforms (no Gram matrix on this
 // side: every assignment's remix is formed sample by sample).  Built and run by tools/hostsim_mixit.py, plain or with

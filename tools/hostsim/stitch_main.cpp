@@ -1,5 +1,5 @@
 // Stand-alone driver for the host simulation of the stitching kernels (csrc/stitch.hip: sep_stitch_cost, sep_stitch_chain, sep_stitch_ola; sep_assign
-// of csrc/loss.hip between them): window geometries around the wave width and the 16-byte paths, n in {1, 3, 9, 20, 64}, every buffer allocated to its
+// of csrc/assign.hip between them): window geometries around the wave width and the 16-byte paths, n in {1, 3, 9, 20, 64}, every buffer allocated to its
 // exact size and pre-filled with NaN (or -7), checked against the contract of include/sepkernels.h restated here with plain double loops.  Built
 // and run by tools/hostsim_stitch.py, plain or with -fsanitize=address,undefined (a program of its own: the sanitizer's runtime is linked in,
 // nothing is preloaded).  Exit status 0 = all within the bounds.

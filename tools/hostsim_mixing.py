@@ -14,56 +14,21 @@ of bounds on exactly-sized filter buffers.
 
 build_library(workdir) gives tests/test_dynamic_mixing_cpu.py a host-simulation library of csrc/mixing.hip and csrc/runtime.hip alone (the
 recorded-sequence case there needs csrc/sequence.hip and with it every file: tools/hostsim.py::build)."""
-import os
-import subprocess
 import sys
-import tempfile
 
 import hostsim
-from hostsim_bss import HOSTSIM_DIR, _includes
 
 FILES = ("mixing", "runtime")
 
 
-def _sources(d):
-    """the host copies of mixing.hip and runtime.hip in `d`, plus the simulation's runtime"""
-    out = []
-    for f in FILES:
-        out.append(os.path.join(d, f + ".cpp"))
-        open(out[-1], "w").write(hostsim.host_copy(f + ".hip"))
-    return out + [os.path.join(HOSTSIM_DIR, "sim_main.cpp")]
-
-
 def build_library(workdir):
     """-> path of a shared library with the entry points of csrc/mixing.hip and csrc/runtime.hip, for hostsim.HostSimBackend"""
-    cxx = hostsim.compiler()
-    if cxx is None:
-        raise RuntimeError("hostsim needs clang++")
-    so = os.path.join(workdir, "libsepkernels_hostsim_mixing.so")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-fPIC", "-pthread", "-shared"] + _includes(workdir) + _sources(workdir) + ["-o", so])
-    return so
+    return hostsim.build_units(workdir, FILES, "mixing")
 
 
 def main():
-    kind = "address,undefined" if "--asan" in sys.argv else None
-    cxx = hostsim.compiler()
-    if cxx is None:
-        print("needs clang++")
-        return 1
-    flags = ["-std=c++17", "-O1", "-pthread"] + (["-g", "-fsanitize=" + kind, "-fno-omit-frame-pointer"] if kind else [])
-    with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "mixing_host")
-        driver = "mixing_speed_main.cpp" if "--speed" in sys.argv else "mixing_main.cpp"
-        subprocess.check_call([cxx] + flags + _includes(d) + _sources(d) + [os.path.join(HOSTSIM_DIR, driver), "-o", exe])
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-        r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=900)
-    markers = ("ERROR: AddressSanitizer", "runtime error:") if kind else ()
-    reports = sum(r.stderr.count(mk) for mk in markers)
-    print(r.stdout[-3000:])
-    if reports or r.returncode:
-        print(r.stderr[-6000:])
-    print("{}: exit status {}, sanitizer reports: {}".format(kind or "plain", r.returncode, reports))
-    return 1 if reports or r.returncode else 0
+    driver = "mixing_speed_main.cpp" if "--speed" in sys.argv else "mixing_main.cpp"
+    return hostsim.run_program(FILES, driver, "mixing_host", "--asan" in sys.argv)
 
 
 if __name__ == "__main__":

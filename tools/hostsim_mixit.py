@@ -1,4 +1,4 @@
-"""Development tool: the MixIT kernels (csrc/loss.hip: sep_mixit_gram, sep_mixit_search, sep_mixit_bwd) compiled for the host (tools/hostsim.py::host_copy,
+"""Development tool: the MixIT kernels (csrc/mixit.hip: sep_mixit_gram, sep_mixit_search, sep_mixit_bwd) compiled for the host (tools/hostsim.py::host_copy,
 the stand-in HIP header of tools/hostsim/include) and linked with tools/hostsim/mixit_main.cpp into ONE PROGRAM that runs the three kernels at
 R = M + N in {2, 10, 24} and T in {1, 2 SEP_MIXIT_SLAB + 17} on exactly-sized buffers against plain double loops.  With --asan the program is
 built with -fsanitize=address,undefined (the runtime is linked in; nothing is preloaded and no Python is involved in the run): reads beyond a
@@ -6,35 +6,21 @@ row's end, writes beyond the scratch or the outputs, undefined arithmetic.
 
     python tools/hostsim_mixit.py [--asan]
 
-build_library(workdir) gives tests/test_mixit_cpu.py a host-simulation library of csrc/loss.hip and csrc/runtime.hip alone."""
-import os
-import subprocess
+build_library(workdir) gives tests/test_mixit_cpu.py a host-simulation library of csrc/mixit.hip, csrc/bss.hip and csrc/runtime.hip alone."""
 import sys
-import tempfile
 
 import hostsim
-from hostsim_bss import HOSTSIM_DIR, _includes, _sources, build_library      # noqa: F401  (the same translation units: csrc/loss.hip, csrc/runtime.hip)
+
+FILES = ("mixit", "bss", "runtime")      # the kernels; bss_reduce_kernel, which adds the Gram pass's slabs; the library's error slot
+
+
+def build_library(workdir):
+    """-> path of a shared library with the entry points of csrc/mixit.hip, csrc/bss.hip and csrc/runtime.hip, for hostsim.HostSimBackend"""
+    return hostsim.build_units(workdir, FILES, "mixit")
 
 
 def main():
-    kind = "address,undefined" if "--asan" in sys.argv else None
-    cxx = hostsim.compiler()
-    if cxx is None:
-        print("needs clang++")
-        return 1
-    flags = ["-std=c++17", "-O1", "-pthread"] + (["-g", "-fsanitize=" + kind, "-fno-omit-frame-pointer"] if kind else [])
-    with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "mixit_host")
-        subprocess.check_call([cxx] + flags + _includes(d) + _sources(d) + [os.path.join(HOSTSIM_DIR, "mixit_main.cpp"), "-o", exe])
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-        r = subprocess.run([exe], env=env, capture_output=True, text=True)
-    markers = ("ERROR: AddressSanitizer", "runtime error:") if kind else ()
-    reports = sum(r.stderr.count(mk) for mk in markers)
-    print(r.stdout[-3000:])
-    if reports or r.returncode:
-        print(r.stderr[-6000:])
-    print("{}: exit status {}, sanitizer reports: {}".format(kind or "plain", r.returncode, reports))
-    return 1 if reports or r.returncode else 0
+    return hostsim.run_program(FILES, "mixit_main.cpp", "mixit_host", "--asan" in sys.argv)
 
 
 if __name__ == "__main__":

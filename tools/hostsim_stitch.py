@@ -1,5 +1,5 @@
 """Development tool: the stitching kernels (csrc/stitch.hip: sep_stitch_cost, sep_stitch_chain, sep_stitch_ola) and sep_assign beside them
-(csrc/loss.hip; csrc/runtime.hip holds the library's error slot) compiled for the host (tools/hostsim.py::host_copy, the stand-in HIP header of
+(csrc/assign.hip; csrc/runtime.hip holds the library's error slot) compiled for the host (tools/hostsim.py::host_copy, the stand-in HIP header of
 tools/hostsim/include) and linked with tools/hostsim/stitch_main.cpp into ONE PROGRAM that runs the three kernels over the window geometries of
 tests/test_longform_gpu.py at n in {1, 3, 9, 20, 64} on exactly-sized buffers against plain double loops, and the four launches in a row on
 scrambled windows.  With --asan the program is built with -fsanitize=address,undefined (the runtime is linked in; nothing is preloaded and no
@@ -8,56 +8,21 @@ permutation entry, undefined arithmetic.
 
     python tools/hostsim_stitch.py [--asan]
 
-build_library(workdir) gives tests/test_longform_cpu.py a host-simulation library of csrc/stitch.hip, csrc/loss.hip and csrc/runtime.hip alone."""
-import os
-import subprocess
+build_library(workdir) gives tests/test_longform_cpu.py a host-simulation library of csrc/stitch.hip, csrc/assign.hip and csrc/runtime.hip alone."""
 import sys
-import tempfile
 
 import hostsim
-from hostsim_bss import HOSTSIM_DIR, _includes
 
-FILES = ("stitch", "loss", "runtime")
-
-
-def _sources(d):
-    """the host copies of stitch.hip, loss.hip and runtime.hip in `d`, plus the simulation's runtime"""
-    out = []
-    for f in FILES:
-        out.append(os.path.join(d, f + ".cpp"))
-        open(out[-1], "w").write(hostsim.host_copy(f + ".hip"))
-    return out + [os.path.join(HOSTSIM_DIR, "sim_main.cpp")]
+FILES = ("stitch", "assign", "runtime")
 
 
 def build_library(workdir):
-    """-> path of a shared library with the entry points of csrc/stitch.hip, csrc/loss.hip and csrc/runtime.hip, for hostsim.HostSimBackend"""
-    cxx = hostsim.compiler()
-    if cxx is None:
-        raise RuntimeError("hostsim needs clang++")
-    so = os.path.join(workdir, "libsepkernels_hostsim_stitch.so")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-fPIC", "-pthread", "-shared"] + _includes(workdir) + _sources(workdir) + ["-o", so])
-    return so
+    """-> path of a shared library with the entry points of csrc/stitch.hip, csrc/assign.hip and csrc/runtime.hip, for hostsim.HostSimBackend"""
+    return hostsim.build_units(workdir, FILES, "stitch")
 
 
 def main():
-    kind = "address,undefined" if "--asan" in sys.argv else None
-    cxx = hostsim.compiler()
-    if cxx is None:
-        print("needs clang++")
-        return 1
-    flags = ["-std=c++17", "-O1", "-pthread"] + (["-g", "-fsanitize=" + kind, "-fno-omit-frame-pointer"] if kind else [])
-    with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "stitch_host")
-        subprocess.check_call([cxx] + flags + _includes(d) + _sources(d) + [os.path.join(HOSTSIM_DIR, "stitch_main.cpp"), "-o", exe])
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-        r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=900)
-    markers = ("ERROR: AddressSanitizer", "runtime error:") if kind else ()
-    reports = sum(r.stderr.count(mk) for mk in markers)
-    print(r.stdout[-3000:])
-    if reports or r.returncode:
-        print(r.stderr[-6000:])
-    print("{}: exit status {}, sanitizer reports: {}".format(kind or "plain", r.returncode, reports))
-    return 1 if reports or r.returncode else 0
+    return hostsim.run_program(FILES, "stitch_main.cpp", "stitch_host", "--asan" in sys.argv)
 
 
 if __name__ == "__main__":
